@@ -2,6 +2,8 @@
 """Headline benchmark of the MI355X ReLU-Fields render path.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (+ what the last timed step returned, as DIR/<name>.npy: two builds compare
+                                                            output for output; the inputs are seeded, the same on every run)
 
 Workload (BASELINE.json: "ray-samples/sec (fwd+bwd) ... 800x800 @ 128^3 grid", configs[2]/[3]):
 one STEP = one training iteration of the posed-image trainer on a 128^3 SH-degree-2 ReLU field -- a random 16384-ray batch
@@ -330,11 +332,14 @@ def load_pmc_table():
 
 
 def respawn_under_torchrun(gpus: int):
-    """``python bench.py --gpus N`` with N > 1 and no torchrun environment: re-exec this command as N ranks (one per GPU, RCCL)
-    under torch.distributed.run on 127.0.0.1.  Never silently runs fewer ranks than asked for."""
+    """``python bench.py --gpus N`` with N > 1 and no torchrun environment: run this command as N ranks (one per GPU, RCCL) under
+    torch.distributed.run on 127.0.0.1, in a fresh child process (this one may have opened the GPU to count devices: it is not
+    replaced by exec), and leave with its exit code.  Never silently runs fewer ranks than asked for."""
+    import signal
     import socket
+    import subprocess
 
-    if torch.cuda.device_count() < gpus and os.environ.get("RF_SINGLE_DEVICE") != "1":  # (test hook: every rank on device 0, over gloo)
+    if os.environ.get("RF_SINGLE_DEVICE") != "1" and torch.cuda.device_count() < gpus:  # (test hook: every rank on device 0, over gloo)
         raise SystemExit(f"--gpus {gpus} but only {torch.cuda.device_count()} HIP device(s) are visible")
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -343,7 +348,24 @@ def respawn_under_torchrun(gpus: int):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # told to stop (a launcher's timeout, ^C): torch.distributed.run gets the signal and ends its ranks, nothing is left running.  The
+    # handlers are in place before the child starts; a signal that comes first is passed on as soon as the child exists.
+    current = {"child": None, "signum": None}
+
+    def stop(signum, _frame):
+        current["signum"] = signum
+        if current["child"] is not None:
+            current["child"].send_signal(signum)
+
+    for sig in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
+        signal.signal(sig, stop)
+    if current["signum"] is not None:
+        sys.exit(128 + current["signum"])
+    current["child"] = subprocess.Popen(cmd)
+    if current["signum"] is not None:
+        current["child"].send_signal(current["signum"])
+    rc = current["child"].wait()
+    sys.exit(128 - rc if rc < 0 else rc)  # (a launcher ended by signal N exits 128 + N, as a shell reports it)
 
 
 def cpu_baseline(grid, rays_cpu, pixels_cpu, num_samples, n_train, n_fwd, threads=0, reps=3, n_full=16384):
@@ -648,6 +670,19 @@ def train_leg_at_reference_final_stage(args, dev, dataset, bounds):
     return leg
 
 
+def dump_outputs(out_dir, stats):
+    """--dump-outputs: what the timed path hands its caller after its last step -- TrainStepper.step returns a StepStats, and its four
+    figures are written as float64 DIR/<name>.npy (specular_loss, diffuse_loss, specular_mse, diffuse_mse).  The inputs are the same
+    on every run (seeded grids, images, ray keys and image batches).  The step itself is not bit-reproducible: its gradient records
+    take their places in a brick's list from atomic cursors, so they are summed in a different order on every run, and Adam carries
+    the rounding on -- two runs agree to a few float32 ulps after 30 steps and drift apart (up to 1.3 %) by 250."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name in ("specular_loss", "diffuse_loss", "specular_mse", "diffuse_mse"):
+        value = getattr(stats, name)
+        if value is not None:
+            np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(float(value), dtype=np.float64))
+
+
 def run_guarded(fn, timeout_s, dev):
     """``fn()`` on a helper thread, waited for at most ``timeout_s``: (result, None), or (None, why) when it raised or is still
     running -- a collective another rank never enters must not cost the line of a run whose timed region is already done."""
@@ -708,7 +743,11 @@ def main():
     ap.add_argument("--second-point-rays", type=int, default=32768, help="rays per GPU of the second weak-scaling point timed behind the windows (0 = skip)")
     ap.add_argument("--windows", type=int, default=9, help="further windows of --steps steps timed behind the official one (ms_per_step_windows)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads for cpu_baseline (0 = the cgroup CPU quota, at most 64)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (its StepStats: losses and MSEs) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         respawn_under_torchrun(args.gpus)  # does not return
@@ -1009,6 +1048,8 @@ def main():
     ops.KERNEL_TIMER = None
     stepper.step_events = None
     stepper.phase_events = None
+    if args.dump_outputs and rank == 0:  # (outside the timed region, before the windows below train the grid further)
+        dump_outputs(args.dump_outputs, stats)
     exchange_bytes = 0
     if owner and stepper.exchange_bytes:  # measured: record slices + offset tables + parameter chunks this rank sent, mean of the last steps
         exchange_bytes = int(np.mean(stepper.exchange_bytes))

@@ -170,3 +170,28 @@ def test_bench_line_contract(hip_device):
     assert cpu["kind"] == "port" and cpu["unit"] == "ray-samples/s" and cpu["value"] > 0 and cpu["cores"] >= 1 and "sample" in cpu
     assert cpu["cfg1_full_frame"]["max_abs_colour_difference_gpu_vs_cpu"] <= 1e-5
     assert line["fwd_render"]["init_field"]["render_launches_per_frame"] == 1
+
+
+def test_bench_dump_outputs(hip_device, tmp_path):
+    """bench.py --dump-outputs DIR: after the timed steps, the four figures of the StepStats the LAST timed step returned, one float64
+    DIR/<name>.npy each -- the same step whose specular MSE the line reports as final_specular_psnr, although a further window trains
+    the grid on before the line is printed."""
+    import json
+    import math
+
+    out = tmp_path / "dump"
+    r = _run([os.path.join(REPO_ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--grid", "64", "--rays", "4096", "--samples", "64",
+              "--image-size", "200", "--cpu-rays", "0", "--render-frames", "0", "--highres-frames", "0", "--dropin-steps", "0", "--train256-steps", "0",
+              "--second-point-rays", "0", "--windows", "1", "--dump-outputs", str(out)], timeout=900)
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+    line = json.loads(lines[0])
+    names = ["diffuse_loss.npy", "diffuse_mse.npy", "specular_loss.npy", "specular_mse.npy"]
+    assert sorted(os.listdir(out)) == names
+    vals = {}
+    for n in names:
+        a = np.load(out / n, allow_pickle=False)
+        assert a.dtype == np.float64 and a.shape == () and os.path.getsize(out / n) < 1024 and np.isfinite(a) and float(a) > 0.0, (n, a)
+        vals[n[:-4]] = float(a)
+    assert vals["specular_mse"] <= vals["specular_loss"] <= 1.0 and vals["diffuse_mse"] <= vals["diffuse_loss"] <= 1.0  # (errors on [0, 1])
+    np.testing.assert_allclose(-10.0 * math.log10(vals["specular_mse"]), line["final_specular_psnr"], rtol=1e-5)

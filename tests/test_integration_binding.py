@@ -1,7 +1,7 @@
 """The reference-side binding of INTEGRATION.md (integration/renderers_hip.py): the file a maintainer of the reference would add.
 
-CPU part (here): its struct mirrors have the sizes the library reports, and -- when the reference checkout is present (the build
-container only) -- it imports against the REAL reference package and describes a real reference VoxelGrid.
+CPU part (here): its struct mirrors have the sizes the library reports, and it follows what the reference package gives it (names,
+grid attributes, AABB and normalisation, recorded from the reference as golden G14) and describes such a grid.
 GPU part: the binding and the package's own duck-typed procedure render a stand-in module that has exactly the reference
 VoxelGrid's attributes, against the golden vectors G7 (outputs of the reference renderer) including gradients."""
 import ctypes as C
@@ -18,32 +18,24 @@ from tests.helpers import REPO_ROOT, hotdog_like_camera, load_golden, procedural
 from thr3ed_atom_amd import _lib
 
 BINDING = os.path.join(REPO_ROOT, "integration", "renderers_hip.py")
-REFERENCE = "/root/reference"
 
 
-def _load_binding(monkeypatch, with_reference: bool):
-    """import integration/renderers_hip.py either against the real reference package or against stand-ins for the three
-    reference names it imports (this package's Rays / RenderOut have the same fields)."""
+def _load_binding(monkeypatch):
+    """import integration/renderers_hip.py against stand-ins for the three reference names it imports (this package's Rays /
+    RenderOut have the same fields: golden G14 holds the reference's)."""
     monkeypatch.setenv("RELU_FIELD_HIP_LIB", _lib.LIB_PATH)
-    if with_reference:
-        monkeypatch.syspath_prepend(REFERENCE)
-        if "easydict" not in sys.modules:  # imported by the reference for a type annotation only
-            ed = types.ModuleType("easydict")
-            ed.EasyDict = dict
-            monkeypatch.setitem(sys.modules, "easydict", ed)
-    else:
-        import thr3ed_atom_amd as rf
-        from thr3ed_atom_amd import constants
+    import thr3ed_atom_amd as rf
+    from thr3ed_atom_amd import constants
 
-        names = ["thre3d_atom", "thre3d_atom.rendering", "thre3d_atom.rendering.volumetric", "thre3d_atom.rendering.volumetric.render_interface",
-                 "thre3d_atom.utils", "thre3d_atom.utils.constants"]
-        mods = {n: types.ModuleType(n) for n in names}
-        mods["thre3d_atom.rendering.volumetric.render_interface"].Rays = rf.Rays
-        mods["thre3d_atom.rendering.volumetric.render_interface"].RenderOut = rf.RenderOut
-        mods["thre3d_atom.utils.constants"].EXTRA_DISPARITY = constants.EXTRA_DISPARITY
-        mods["thre3d_atom.utils.constants"].EXTRA_ACCUMULATED_WEIGHTS = constants.EXTRA_ACCUMULATED_WEIGHTS
-        for n, m in mods.items():
-            monkeypatch.setitem(sys.modules, n, m)
+    names = ["thre3d_atom", "thre3d_atom.rendering", "thre3d_atom.rendering.volumetric", "thre3d_atom.rendering.volumetric.render_interface",
+             "thre3d_atom.utils", "thre3d_atom.utils.constants"]
+    mods = {n: types.ModuleType(n) for n in names}
+    mods["thre3d_atom.rendering.volumetric.render_interface"].Rays = rf.Rays
+    mods["thre3d_atom.rendering.volumetric.render_interface"].RenderOut = rf.RenderOut
+    mods["thre3d_atom.utils.constants"].EXTRA_DISPARITY = constants.EXTRA_DISPARITY
+    mods["thre3d_atom.utils.constants"].EXTRA_ACCUMULATED_WEIGHTS = constants.EXTRA_ACCUMULATED_WEIGHTS
+    for n, m in mods.items():
+        monkeypatch.setitem(sys.modules, n, m)
     spec = importlib.util.spec_from_file_location("renderers_hip_under_test", BINDING)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
@@ -53,7 +45,7 @@ def _load_binding(monkeypatch, with_reference: bool):
 def test_binding_struct_mirrors_match_the_library(monkeypatch):
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
-    rh = _load_binding(monkeypatch, with_reference=False)
+    rh = _load_binding(monkeypatch)
     lib = rh._library()
     lib.rf_abi_struct_size.argtypes = [C.c_int]
     for which, mirror in ((0, rh.RFGrid), (1, rh.RFRayBatch), (2, rh.RFRenderOut), (3, rh.RFRenderGrads), (4, rh.RFBrickList), (6, rh.RFCamera), (8, rh.RFPassScratch)):
@@ -63,13 +55,28 @@ def test_binding_struct_mirrors_match_the_library(monkeypatch):
         assert lib.rf_abi_struct_size(which) == C.sizeof(mirror)
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "thre3d_atom")), reason="reference checkout not present (GPU box)")
-def test_binding_imports_against_the_real_reference_and_describes_its_grid(monkeypatch):
-    rh = _load_binding(monkeypatch, with_reference=True)
-    from thre3d_atom.thre3d_reprs.voxels import VoxelGrid as RefGrid, VoxelGridLocation as RefLoc, VoxelSize as RefSize
+def test_binding_follows_the_recorded_reference_api_and_describes_its_grid(monkeypatch):
+    """What the binding relies on in the reference package, recorded from it as data (golden G14, oracle/gen_golden_binding.py): the
+    names it imports match the stand-ins it is loaded against, every attribute of the stand-in grid the GPU tests render through is one
+    a reference VoxelGrid has, and that grid is described with the reference's own AABB and normalisation."""
+    import dataclasses
 
-    g = RefGrid(torch.rand(4, 5, 6, 1), torch.rand(4, 5, 6, 27), RefSize(0.1, 0.2, 0.3), RefLoc(0.5, 0.0, -0.25),
-                density_preactivation=torch.nn.Identity(), density_postactivation=torch.nn.ReLU(), expected_density_scale=7.0, tunable=True)
+    import thr3ed_atom_amd as rf
+    from thr3ed_atom_amd import constants
+
+    g14 = load_golden("g14_binding_api.npz")
+    assert [f.name for f in dataclasses.fields(rf.Rays)] == list(g14["rays_fields"])
+    assert [f.name for f in dataclasses.fields(rf.RenderOut)] == list(g14["render_out_fields"])
+    assert constants.EXTRA_DISPARITY == str(g14["extra_disparity"]) and constants.EXTRA_ACCUMULATED_WEIGHTS == str(g14["extra_accumulated_weights"])
+
+    rh = _load_binding(monkeypatch)
+    g = _ReferenceLikeGrid(torch.rand(4, 5, 6, 1), torch.rand(4, 5, 6, 27), (0.1, 0.2, 0.3), (0.5, 0.0, -0.25), torch.nn.Identity(), torch.nn.ReLU(), 7.0)
+    # every name the stand-in holds -- what all the GPU binding tests render through -- is one a reference VoxelGrid holds (collected
+    # the way oracle/gen_golden_binding.py collects the reference's)
+    held = (set(vars(g)) - set(vars(torch.nn.Module()))) | set(g._parameters) | set(g._modules)
+    held |= {n for n in dir(type(g)) if isinstance(getattr(type(g), n, None), property)}
+    assert held <= set(g14["grid_attributes"].tolist()), held - set(g14["grid_attributes"].tolist())
+    assert np.array_equal(np.array(g.aabb, dtype=np.float64), g14["grid_aabb"])
     d = rh._describe_grid(g, g.densities, g.features)
     assert list(d.dims) == [4, 5, 6] and d.num_features == 27 and d.layout == 0 and d.density_mode == 0
     assert abs(d.aabb_min[0] - 0.3) < 1e-6 and abs(d.aabb_max[2] - 0.65) < 1e-6
@@ -83,12 +90,12 @@ def test_binding_imports_against_the_real_reference_and_describes_its_grid(monke
     for a in range(3):
         scale, bias = slack_range_map(tuple(g.aabb[a]))
         assert d.norm_scale[a] == float(scale) and d.norm_bias[a] == float(bias)
+    # x * scale + bias in float32 is the reference's own VoxelGrid._normalize_points, bit for bit
+    pts = g14["grid_points"]
+    mapped = pts * np.array(d.norm_scale, dtype=np.float32) + np.array(d.norm_bias, dtype=np.float32)
+    np.testing.assert_array_equal(mapped, g14["grid_normalized"])
     with pytest.raises(RuntimeError, match="HIP device"):
-        from thre3d_atom.rendering.volumetric.render_interface import Rays as RefRays
-        from thre3d_atom.thre3d_reprs.renderers import SHVoxGridRenderConfig as RefCfg
-        from thre3d_atom.utils.imaging_utils import CameraBounds as RefBounds
-
-        rh.render_sh_voxel_grid_hip(g, RefRays(torch.zeros(3, 3), torch.ones(3, 3)), RefCfg(8, RefBounds(0.5, 4.0)))
+        rh.render_sh_voxel_grid_hip(g, rf.Rays(torch.zeros(3, 3), torch.ones(3, 3)), rf.SHVoxGridRenderConfig(8, rf.CameraBounds(0.5, 4.0)))
 
 
 class _ReferenceLikeGrid(torch.nn.Module):
@@ -132,7 +139,7 @@ def test_reference_like_module_renders_like_the_reference(hip_device, monkeypatc
     if via.startswith("binding"):
         # ("binding-binned": the atomic-free adjoint the binding picks for training-size renders, forced here on the small one)
         monkeypatch.setenv("RELU_FIELD_HIP_BACKWARD", "binned" if via == "binding-binned" else "atomic")
-        rh = _load_binding(monkeypatch, with_reference=False)
+        rh = _load_binding(monkeypatch)
         out = rh.render_sh_voxel_grid_hip(grid, rays, cfg)
     else:
         out = rf.render_sh_voxel_grid(grid, rays, cfg)
@@ -163,7 +170,7 @@ def test_binding_frame_entry_equals_the_ray_list_procedure(hip_device, monkeypat
     pose = rf.pose_spherical(25.0, -35.0, cam["radius"])
     rays = rf.flatten_rays(rf.cast_rays(intr, pose, hip_device))
     monkeypatch.setenv("RF_FRAME_TILES", tiles)
-    rh = _load_binding(monkeypatch, with_reference=False)
+    rh = _load_binding(monkeypatch)
     for edit in (False, True):
         if edit:
             with torch.no_grad():
@@ -189,7 +196,7 @@ def test_binding_pair_procedure_equals_two_calls_and_follows_golden_g7(hip_devic
     import thr3ed_atom_amd as rf
 
     monkeypatch.setenv("RELU_FIELD_HIP_BACKWARD", "binned")
-    rh = _load_binding(monkeypatch, with_reference=False)
+    rh = _load_binding(monkeypatch)
     g7 = load_golden("g7_grid16_render.npz")
     cam = hotdog_like_camera()
     dens, feat = procedural_grid((16, 16, 16), 27, 81)
@@ -229,7 +236,7 @@ def test_binding_split_shadow_hooks(hip_device, monkeypatch):
     counters; a write that bumps neither (``p.data.mul_``) needs ``invalidate_split_shadow``; ``release_split_shadow`` frees the copy."""
     import thr3ed_atom_amd as rf
 
-    rh = _load_binding(monkeypatch, with_reference=False)
+    rh = _load_binding(monkeypatch)
     g7 = load_golden("g7_grid16_render.npz")
     cam = hotdog_like_camera()
     dens, feat = procedural_grid((16, 16, 16), 27, 81)
