@@ -77,6 +77,12 @@ def density_kwargs(mode, rho):
             density_postactivation=torch.nn.Softplus(),
             expected_density_scale=rho,
         )
+    if mode == "identity":
+        return dict(
+            density_preactivation=torch.nn.Identity(),
+            density_postactivation=torch.nn.Identity(),
+            expected_density_scale=rho,
+        )
     return dict(
         density_preactivation=torch.abs,
         density_postactivation=torch.nn.Identity(),
@@ -388,6 +394,92 @@ def g13_last_sample_inside():
     save("g13_last_sample_inside.npz", near=np.float64(1.0), far=np.float64(3.4), **out)
 
 
+G15_DIMS, G15_F, G15_SEED, G15_RHO, G15_S = (12, 12, 12), 27, 151, 12.0, 48
+
+
+def g15_identity_density():
+    """Identity/Identity densities (the fourth mode of the C ABI): sigma is signed, and where sigma delta < 0 the occupancy
+    alpha = 1 - exp(-sigma delta) is negative and the transmittance grows above 1.  The field (tests/helpers.py signed_density_grid) is
+    positive on the whole with negative pockets; the rays are the first 160 of 256 whose float64 transmittance stays below 8 and whose
+    last sample (interval 1e10 |d|) lies outside the box.  Three render configurations (white, black background, stratified jitter from
+    a stored table) with the reference's float32 outputs and gradients of an L1 loss and its float64 outputs and density gradient; plus
+    VoxelGrid.forward in identity mode on G3's anisotropic grid and 2048 points."""
+    from oracle import relu_field_oracle as orc
+    from tests.helpers import identity_regime, signed_density_grid
+
+    dens, feat = signed_density_grid(G15_DIMS, G15_F, G15_SEED)
+    voxel = tuple(3.0 / d for d in G15_DIMS)
+    bounds = CameraBounds(1.8, 7.5)
+    aabb = orc.make_aabb(G15_DIMS, voxel)
+    n_all, n = 256, 160
+    o = torch.from_numpy(hash_uniform((n_all, 3), G15_SEED + 1))
+    o = o / o.norm(dim=-1, keepdim=True) * 4.0
+    d = torch.from_numpy(hash_uniform((n_all, 3), G15_SEED + 2)) * 0.8 - o
+    d = d / d.norm(dim=-1, keepdim=True)
+    torch.manual_seed(321)
+    t_rand_all = torch.rand(n_all, G15_S)
+    cases = [("white", dict()), ("black", dict(white_bkgd=False)), ("jitter", dict(perturb_sampled_points=True))]
+
+    def oracle64(o_, d_, t_rand, over):
+        with torch.no_grad():
+            return orc.render(dens.double(), feat.double(), o_.double(), d_.double(), aabb, bounds.near, bounds.far, G15_S, G15_RHO, "identity",
+                              white_bkgd=over.get("white_bkgd", True), t_rand=t_rand.double() if over.get("perturb_sampled_points") else None)
+
+    keep = torch.ones(n_all, dtype=torch.bool)
+    for _, over in cases:
+        r64 = oracle64(o, d, t_rand_all, over)
+        keep &= identity_regime(r64["processed"], r64["deltas"])[2]
+        end = o + float(bounds.far) * d  # (the last sample of the jittered render lies between the last two of the plain one)
+        keep &= ~orc.inside_aabb(end, aabb).reshape(-1)
+    idx = torch.nonzero(keep).reshape(-1)[:n]
+    assert len(idx) == n, int(keep.sum())
+    o, d, t_rand = o[idx].contiguous(), d[idx].contiguous(), t_rand_all[idx].contiguous()
+    target = torch.from_numpy(hash_uniform((n, 3), G15_SEED + 3, 0.0, 1.0))
+    out = {"origins": o, "directions": d, "target": target, "t_rand": t_rand}
+
+    real_rand = torch.rand
+    for tag, over in cases:
+        kw = dict(num_samples_per_ray=G15_S, camera_bounds=bounds, perturb_sampled_points=False, white_bkgd=True)
+        kw.update(over)
+        cfg = SHVoxGridRenderConfig(**kw)
+        # the regime is covered: negative occupancies of -0.5 and below inside the box, a transmittance above 1 but below 8, no
+        # ray whose last sample (1e10-long interval) sits inside the box
+        r64 = oracle64(o, d, t_rand, over)
+        xmin, tmax, usable = identity_regime(r64["processed"], r64["deltas"])
+        x = (r64["processed"][..., 3] * r64["deltas"])[:, :-1]
+        assert bool(usable.all()) and float(tmax.max()) < 8.0 and float(tmax.max()) > 2.0, float(tmax.max())
+        assert int((x <= -0.5).sum()) >= 100 and int((x <= -1.0).sum()) >= 10, (int((x <= -0.5).sum()), int((x <= -1.0).sum()))
+        assert not bool(orc.inside_aabb((o + r64["z"][:, -1:].float() * d), aabb).any())
+        torch.rand = lambda *a, **k: t_rand.to(k.get("dtype") or torch.float32)  # both precisions see the stored jitter table
+        try:
+            grid = make_grid(dens, feat, voxel, mode="identity", rho=G15_RHO, tunable=True)
+            res, loss, gd, gf = run_render(grid, Rays(o, d), cfg, target)
+            grid64 = make_grid(dens.double(), feat.double(), voxel, mode="identity", rho=G15_RHO, tunable=True)
+            r64ref, _, gd64, _ = run_render(grid64, Rays(o, d), cfg, target, torch.float64)
+        finally:
+            torch.rand = real_rand
+        assert torch.isfinite(res.colour).all() and torch.isfinite(gd).all() and torch.isfinite(gf).all()
+        out[f"{tag}_colour"] = res.colour
+        out[f"{tag}_depth"] = res.depth
+        out[f"{tag}_acc"] = res.extra["accumulated_weight"]
+        out[f"{tag}_loss"] = loss
+        out[f"{tag}_gd"] = gd
+        out[f"{tag}_gf"] = gf
+        out[f"{tag}_f64_colour"] = r64ref.colour
+        out[f"{tag}_f64_depth"] = r64ref.depth
+        out[f"{tag}_f64_acc"] = r64ref.extra["accumulated_weight"]
+        out[f"{tag}_f64_gd"] = gd64.float()
+    # VoxelGrid.forward in identity mode on G3's grid and points (G3 itself stays as it is)
+    g3 = np.load(os.path.join(GOLDEN_DIR, "g3_voxel_grid.npz"))
+    adens, afeat = procedural_grid((5, 6, 7), 27, 31)
+    agrid = make_grid(adens, afeat, tuple(g3["aniso_voxel"]), tuple(g3["aniso_loc"]), "identity", float(g3["aniso_rho"]))
+    pts = boundary_points(agrid.aabb, 2048, 41)
+    assert np.array_equal(pts.numpy(), g3["aniso_points"])
+    out["aniso_identity"] = agrid(pts)
+    assert float(out["aniso_identity"][:, -1].min()) < 0.0  # signed densities
+    save("g15_identity_density.npz", near=np.float64(bounds.near), far=np.float64(bounds.far), rho=np.float64(G15_RHO), **out)
+
+
 def g11_density_noise():
     """stochastic_density_noise_std != 0 (accumulate.py:58-62): with perturb_sampled_points off the render's only RNG draw is
     torch.randn(N, S), so the noise table is reproducible from the seed and stored beside the outputs."""
@@ -524,6 +616,7 @@ if __name__ == "__main__":
         "g11": g11_density_noise,
         "g12": g12_plugins,
         "g13": g13_last_sample_inside,
+        "g15": g15_identity_density,
     }
     for name, fn in jobs.items():
         if not wanted or name in wanted:

@@ -47,6 +47,27 @@ def sparse_scene_grid(dims, num_features: int, seed: int):
     return torch.from_numpy(dens), torch.from_numpy(feat)
 
 
+def signed_density_grid(dims, num_features: int, seed: int, bias: float = 0.5, pocket_gain: float = 3.0):
+    """A density field for the Identity/Identity mode, where sigma may be negative: U(-1,1) + bias, the negative values scaled by
+    pocket_gain -- positive on the whole (rays are attenuated, the transmittance stays moderate) with negative pockets, where
+    sigma * delta reaches -1 and below and alpha = 1 - exp(-sigma delta) < 0.  Features as procedural_grid."""
+    dens, feat = procedural_grid(dims, num_features, seed)
+    dens = dens + np.float32(bias)
+    dens = torch.where(dens < 0, dens * np.float32(pocket_gain), dens)
+    return dens, feat
+
+
+def identity_regime(processed, deltas, t_cap: float = 8.0):
+    """Per ray, from a (float64) oracle render of an identity grid: (min sigma * delta over all samples but the last, max prefix
+    transmittance, usable).  A ray is usable when its last sample -- interval 1e10 |d| -- has sigma >= 0 (a negative one makes the
+    reference's own alpha -inf) and its transmittance stays below t_cap, where the absolute parity bars keep their meaning."""
+    x = torch.cat([(processed[..., 3] * deltas)[:, :-1], torch.zeros_like(deltas[:, :1])], dim=-1)  # (+ a 0: rays of one sample)
+    trans = torch.exp(-torch.cumsum(torch.cat([torch.zeros_like(x[:, :1]), x[:, :-1]], dim=-1), dim=-1))
+    t_max = trans.max(dim=-1).values
+    usable = (processed[:, -1, 3] >= 0) & (t_max <= t_cap)
+    return x.min(dim=-1).values, t_max, usable
+
+
 def hotdog_like_camera():
     """Synthetic camera constants taken from the reference: radius 4.0311
     (data/tests/test_datasets.py:50), near/far 2.0/6.0 (tools/convert_from_nerf_blender_dataset.py:15)

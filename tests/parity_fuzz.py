@@ -1,7 +1,7 @@
 """Randomised parity sweep of the HIP path against the oracle -- test infrastructure (it calls the oracle), on a GPU box:
 
     python -m tests.parity_fuzz [--cases N] [--seed S] [--kind rays|frames|train|misc|composed|binding|long|longframes|longtrain|all]
-                                [--mode relu|softplus|abs] [--only i,j,...] [--verbose]
+                                [--mode relu|softplus|abs|identity] [--only i,j,...] [--verbose]
 
 tests/test_hip_parity_fuzz.py replays a fixed set of its cases.
 
@@ -21,18 +21,48 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import thr3ed_atom_amd as rf  # noqa: E402
 from oracle import relu_field_oracle as orc  # noqa: E402
-from tests.helpers import hash_uniform, procedural_grid  # noqa: E402
+from tests.helpers import hash_uniform, identity_regime, procedural_grid, signed_density_grid  # noqa: E402
 
 TOL = 1e-5
 FORCE_MODE = ""
 LONG_RAYS = False
 BIG_GRIDS = False
-ACTS = {"relu": (torch.nn.Identity(), torch.nn.ReLU()), "softplus": (torch.nn.Identity(), torch.nn.Softplus()), "abs": (torch.abs, torch.nn.Identity())}
+ACTS = {"relu": (torch.nn.Identity(), torch.nn.ReLU()), "softplus": (torch.nn.Identity(), torch.nn.Softplus()), "abs": (torch.abs, torch.nn.Identity()),
+        "identity": (torch.nn.Identity(), torch.nn.Identity())}
+# Identity/Identity densities are signed (never drawn at random: --mode identity / run_case(..., mode="identity")).  Their grids follow
+# tests/helpers.py signed_density_grid, and a ray enters the comparison only if the float64 oracle keeps its transmittance below 8 and
+# its last sample (interval 1e10 |d|) off a negative density -- there the reference's own alpha is -inf.  Per identity case:
+# (usable rays, rays, min sigma delta over the usable rays), for the replay's non-vacuity check.
+IDENTITY_STATS = []
 
 
 def make_grid(dev, dens, feat, voxel, loc, mode, rho, storage, tunable):
     return rf.VoxelGrid(dens.clone().to(dev), feat.clone().to(dev), rf.VoxelSize(*voxel), rf.VoxelGridLocation(*loc), density_preactivation=ACTS[mode][0],
                         density_postactivation=ACTS[mode][1], expected_density_scale=rho, tunable=tunable, storage=storage)
+
+
+def draw_grid(dims, F, seed, mode):
+    return signed_density_grid(dims, F, seed % 100000) if mode == "identity" else procedural_grid(dims, F, seed % 100000)
+
+
+def identity_usable(dens, feat, o, d, aabb, near, far, S, rho, white, diffuse=False, opt=False, t_rand=None, jitter_unknown=False):
+    """rays of an identity case that enter the comparison (see IDENTITY_STATS), from the oracle: the transmittance in float64, the last
+    sample in float32 as well (with AABB sampling it lies ON the exit face, where the two precisions may disagree on `inside`).
+    jitter_unknown: the render jitters with a table not drawn yet -- the ray must also have left the box before the last bin starts."""
+    with torch.no_grad():
+        r64 = orc.render(dens.double(), feat.double(), o.double(), d.double(), aabb, near, far, S, rho, "identity", white_bkgd=white, render_diffuse=diffuse,
+                         optimized_sampling=opt, t_rand=None if t_rand is None else t_rand.double())
+        r32 = orc.render(dens, feat, o, d, aabb, near, far, S, rho, "identity", white_bkgd=white, render_diffuse=diffuse, optimized_sampling=opt, t_rand=t_rand)
+    xmin, _, usable = identity_regime(r64["processed"], r64["deltas"])
+    usable &= (r32["processed"][:, -1, 3] >= 0) & torch.isfinite(r32["colour"]).all(dim=-1)
+    # (and sum |w| <= 3: weights alpha T of either sign, |alpha| up to e^|x| - 1, cancel in the float32 sums of both sides -- beyond a few
+    # units that noise alone reaches the absolute bars, which were set for 0 <= w, sum w <= 1)
+    usable &= r64["weights"].abs().sum(dim=-1) <= 3.0
+    if jitter_unknown and S > 1:
+        bounds, hit = orc.ray_aabb_bounds(o, d, near, far, aabb)
+        usable &= ~hit.reshape(-1) | (bounds[:, 1] < r64["z"][:, -2].float())
+    IDENTITY_STATS.append((int(usable.sum()), len(usable), float(xmin[usable].min()) if bool(usable.any()) else 0.0))
+    return usable
 
 
 def draw_common(rng):
@@ -45,14 +75,17 @@ def draw_common(rng):
     extent = [float(rng.uniform(1.5, 3.5)) for _ in range(3)]
     voxel = tuple(e / d for e, d in zip(extent, dims))
     loc = tuple(float(rng.uniform(-0.3, 0.3)) for _ in range(3))
-    rho = 1.0 if mode == "abs" else float(rng.choice([1.0, 9.0, 100.0 / 3.0]))
+    if mode == "identity":
+        rho = float(rng.choice([2.0, 5.0, 10.0]))
+    else:
+        rho = 1.0 if mode == "abs" else float(rng.choice([1.0, 9.0, 100.0 / 3.0]))
     return dims, deg, mode, storage, voxel, loc, rho
 
 
 def case_rays(rng, dev, seed):
     dims, deg, mode, storage, voxel, loc, rho = draw_common(rng)
     F = 3 * (deg + 1) ** 2
-    dens, feat = procedural_grid(dims, F, seed % 100000)
+    dens, feat = draw_grid(dims, F, seed, mode)
     n = int(rng.integers(1, 400))
     S = int(rng.choice([1, 2, 3, 17, 40, 63, 64, 65, 128, 150]))
     if LONG_RAYS:  # sample counts around the kernels' internal group sizes (64-sample chunks, 64 chunk masks = 4096 samples per mask group)
@@ -73,6 +106,13 @@ def case_rays(rng, dev, seed):
     target = torch.from_numpy(hash_uniform((n, 3), seed + 6, 0.0, 1.0))
     backward = str(rng.choice(["atomic", "binned"]))
     desc = f"rays dims={dims} deg={deg} mode={mode} storage={storage} n={n} S={S} diffuse={diffuse} opt={opt} white={white} perturb={perturb} backward={backward} near={near:.2f}"
+    if mode == "identity":
+        keep = identity_usable(dens, feat, o, d, orc.make_aabb(dims, voxel, loc), near, far, S, rho, white, diffuse, opt, t_rand)
+        if not bool(keep.any()):
+            return desc + " (no usable ray)"
+        o, d, target = o[keep].contiguous(), d[keep].contiguous(), target[keep].contiguous()
+        t_rand = None if t_rand is None else t_rand[keep].contiguous()
+        n = len(o)
     grid = make_grid(dev, dens, feat, voxel, loc, mode, rho, storage, True)
     cfg = rf.SHVoxGridRenderConfig(S, rf.CameraBounds(near, far), perturb_sampled_points=perturb, optimized_sampling=opt, white_bkgd=white, render_diffuse=diffuse)
     from thr3ed_atom_amd import ops
@@ -123,7 +163,7 @@ def case_rays(rng, dev, seed):
 def case_frames(rng, dev, seed):
     dims, deg, mode, storage, voxel, loc, rho = draw_common(rng)
     F = 3 * (deg + 1) ** 2
-    dens, feat = procedural_grid(dims, F, seed % 100000)
+    dens, feat = draw_grid(dims, F, seed, mode)
     H, W = int(rng.integers(1, 50)), int(rng.integers(1, 50))
     focal = float(rng.choice([20.0, 60.0, 300.0, 900.0]))
     S = int(rng.choice([1, 5, 40, 64, 97]))
@@ -148,6 +188,11 @@ def case_frames(rng, dev, seed):
     finally:
         os.environ.pop("RF_FRAME_TILES", None)
     flat = rf.flatten_rays(rf.cast_rays(intr, pose, dev))
+    rows = slice(None)  # (identity: the pixels whose rays are usable)
+    if mode == "identity":
+        rows = identity_usable(dens, feat, flat.origins.cpu(), flat.directions.cpu(), orc.make_aabb(dims, voxel, loc), near, far, S, rho, white, diffuse, opt)
+        if not bool(rows.any()):
+            return desc + " (no usable ray)"
     ref = orc.render(dens, feat, flat.origins.cpu(), flat.directions.cpu(), orc.make_aabb(dims, voxel, loc), near, far, S, rho, mode, white_bkgd=white,
                      render_diffuse=diffuse, optimized_sampling=opt)
     if LONG_RAYS:  # the float64-anchored rule (see case_rays)
@@ -155,13 +200,13 @@ def case_frames(rng, dev, seed):
                          white_bkgd=white, render_diffuse=diffuse, optimized_sampling=opt)
         for name, ours, bar in (("colour", frame.colour.reshape(-1, 3), TOL), ("depth", frame.depth.reshape(-1, 1), 2 * TOL * max(1.0, far / 6.6)),
                                 ("acc", frame.extra["accumulated_weight"].reshape(-1, 1), TOL)):
-            noise = float((ref[name].double() - r64[name]).abs().max())
-            worst = float((ours.cpu().double() - r64[name]).abs().max())
+            noise = float((ref[name].double() - r64[name])[rows].abs().max())
+            worst = float((ours.cpu().double() - r64[name])[rows].abs().max())
             assert worst <= 3.0 * noise + bar, f"{desc}: {name} is {worst:.2e} from the float64 value; the float32 reference is {noise:.2e} from it"
         return desc
-    err_c = float((frame.colour.reshape(-1, 3).cpu() - ref["colour"]).abs().max())
-    err_a = float((frame.extra["accumulated_weight"].reshape(-1, 1).cpu() - ref["acc"]).abs().max())
-    err_d = float((frame.depth.reshape(-1, 1).cpu() - ref["depth"]).abs().max())
+    err_c = float((frame.colour.reshape(-1, 3).cpu() - ref["colour"])[rows].abs().max())
+    err_a = float((frame.extra["accumulated_weight"].reshape(-1, 1).cpu() - ref["acc"])[rows].abs().max())
+    err_d = float((frame.depth.reshape(-1, 1).cpu() - ref["depth"])[rows].abs().max())
     assert err_c <= TOL and err_a <= TOL and err_d <= 2 * TOL * max(1.0, far / 6.6), f"{desc}: colour {err_c:.2e} acc {err_a:.2e} depth {err_d:.2e}"
     return desc
 
@@ -180,9 +225,12 @@ def case_train(rng, dev, seed):
         mode = FORCE_MODE
     storage = str(rng.choice(["reference", "split", "bricked"]))
     voxel = tuple(3.0 / d for d in dims)
-    rho = 1.0 if mode == "abs" else float(rng.choice([5.0, 100.0 / 3.0]))
+    if mode == "identity":
+        rho = float(rng.choice([2.0, 5.0]))
+    else:
+        rho = 1.0 if mode == "abs" else float(rng.choice([5.0, 100.0 / 3.0]))
     F = 3 * (deg + 1) ** 2
-    dens, feat = procedural_grid(dims, F, seed % 100000)
+    dens, feat = draw_grid(dims, F, seed, mode)
     n = int(rng.choice([1, 3, 37, 64, 130, 257]))
     # (not fewer than 17 samples here: with 2 or 3 the 1e10-long last interval often lies inside the volume and the float32 forward
     # rounding of the REFERENCE itself shows as 1e-4 relative noise on small gradients -- tests/debug_train_case.py: HIP and the float32
@@ -209,6 +257,13 @@ def case_train(rng, dev, seed):
     d = d / d.norm(dim=-1, keepdim=True)
     pixels = torch.from_numpy(hash_uniform((n, 3), seed + 6, 0.0, 1.0))
     near, far = 1.8, 6.6
+    if mode == "identity":  # (both renders of the step: specular and diffuse, jittered by tables drawn below)
+        keep = identity_usable(dens, feat, o, d, orc.make_aabb(dims, voxel), near, far, S, rho, white, jitter_unknown=perturb)
+        keep &= identity_usable(dens, feat, o, d, orc.make_aabb(dims, voxel), near, far, S, rho, white, diffuse=True, jitter_unknown=perturb)
+        if not bool(keep.any()):
+            return desc + " (no usable ray)"
+        o, d, pixels = o[keep].contiguous(), d[keep].contiguous(), pixels[keep].contiguous()
+        n = len(o)
     grid = make_grid(dev, dens, feat, voxel, (0.0, 0.0, 0.0), mode, rho, storage, True)
     cfg = rf.SHVoxGridRenderConfig(S, rf.CameraBounds(near, far), perturb_sampled_points=perturb, white_bkgd=white)
     model = rf.VolumetricModel(grid, rf.render_sh_voxel_grid, cfg, device=dev)
@@ -272,7 +327,7 @@ def case_misc(rng, dev, seed):
     dims, deg, mode, storage, voxel, loc, rho = draw_common(rng)
     F = 3 * (deg + 1) ** 2
     if what == "query":
-        dens, feat = procedural_grid(dims, F, seed % 100000)
+        dens, feat = draw_grid(dims, F, seed, mode)
         m = int(rng.integers(1, 3000))
         lo = np.array([l - 0.5 * v * d_ for l, v, d_ in zip(loc, voxel, dims)], dtype=np.float32)
         hi = np.array([l + 0.5 * v * d_ for l, v, d_ in zip(loc, voxel, dims)], dtype=np.float32)
@@ -511,7 +566,7 @@ def case_binding(rng, dev, seed):
     procedure, the pair procedure and the frame entry, against the oracle."""
     dims, deg, mode, storage, voxel, loc, rho = draw_common(rng)
     F = 3 * (deg + 1) ** 2
-    dens, feat = procedural_grid(dims, F, seed % 100000)
+    dens, feat = draw_grid(dims, F, seed, mode)
     backward = str(rng.choice(["atomic", "binned"]))
     rh = load_binding(backward)
     what = str(rng.choice(["single", "pair", "frame"]))
@@ -531,9 +586,14 @@ def case_binding(rng, dev, seed):
         cfg = rf.SHVoxGridRenderConfig(S, rf.CameraBounds(near, far), perturb_sampled_points=False, optimized_sampling=opt, white_bkgd=white, render_diffuse=diffuse)
         out = rh.render_frame_hip(grid, intr, pose, cfg)
         flat = rf.flatten_rays(rf.cast_rays(intr, pose, dev))
+        rows = slice(None)  # (identity: the pixels whose rays are usable)
+        if mode == "identity":
+            rows = identity_usable(dens, feat, flat.origins.cpu(), flat.directions.cpu(), aabb, near, far, S, rho, white, diffuse, opt)
+            if not bool(rows.any()):
+                return desc + " (no usable ray)"
         ref = orc.render(dens, feat, flat.origins.cpu(), flat.directions.cpu(), aabb, near, far, S, rho, mode, white_bkgd=white, render_diffuse=diffuse, optimized_sampling=opt)
-        err_c = float((out.colour.reshape(-1, 3).cpu() - ref["colour"]).abs().max())
-        err_d = float((out.depth.reshape(-1, 1).cpu() - ref["depth"]).abs().max())
+        err_c = float((out.colour.reshape(-1, 3).cpu() - ref["colour"])[rows].abs().max())
+        err_d = float((out.depth.reshape(-1, 1).cpu() - ref["depth"])[rows].abs().max())
         assert err_c <= TOL and err_d <= 2 * TOL * max(1.0, far / 6.6), f"{desc} HxW={H}x{W}: colour {err_c:.2e} depth {err_d:.2e}"
         return desc
     n = int(rng.integers(1, 300))
@@ -542,6 +602,13 @@ def case_binding(rng, dev, seed):
     d = torch.from_numpy(hash_uniform((n, 3), seed + 3)) * 1.5 - o
     d = d / d.norm(dim=-1, keepdim=True).clamp_min(1e-3) * (1.0 + 0.2 * torch.from_numpy(hash_uniform((n, 1), seed + 4)))
     target = torch.from_numpy(hash_uniform((n, 3), seed + 6, 0.0, 1.0))
+    if mode == "identity":  # (the pair procedure renders specular and diffuse)
+        keep = identity_usable(dens, feat, o, d, aabb, near, far, S, rho, white, opt=opt)
+        keep &= identity_usable(dens, feat, o, d, aabb, near, far, S, rho, white, diffuse=True, opt=opt)
+        if not bool(keep.any()):
+            return desc + " (no usable ray)"
+        o, d, target = o[keep].contiguous(), d[keep].contiguous(), target[keep].contiguous()
+        n = len(o)
     rays = rf.Rays(o.to(dev), d.to(dev))
     dc, fc = dens.clone().requires_grad_(True), feat.clone().requires_grad_(True)
     if what == "single":
@@ -601,7 +668,7 @@ def main():
     ap.add_argument("--kind", default="all")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--only", default="", help="comma-separated case indices (re-run failures)")
-    ap.add_argument("--mode", default="", help="restrict the density mode (relu / softplus / abs)")
+    ap.add_argument("--mode", default="", help="restrict the density mode (relu / softplus / abs / identity)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     fails = 0

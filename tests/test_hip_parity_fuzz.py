@@ -79,3 +79,22 @@ def test_frames_of_256_to_5000_samples(hip_device):
 def test_last_sample_inside_the_volume_softplus_density_gradient(hip_device, run_seed, i, kind, mode):
     desc = parity_fuzz.run_case(run_seed, i, kind, hip_device, mode)
     assert "mode=softplus" in desc
+
+
+@pytest.mark.parametrize("kind,run_seed,count", [("rays", 501, 40), ("frames", 502, 20), ("train", 503, 20), ("binding", 504, 20), ("long", 505, 8)])
+def test_identity_densities(hip_device, kind, run_seed, count):
+    """Identity/Identity densities (signed: negative occupancies where sigma delta < 0, transmittances above 1) in random set-ups of
+    every kind that forms an occupancy: both adjoints, either frame kernel, rf_train_step with its forward / emit pair kernels and the
+    brick pass (with and without Adam in the flush), the reference-side binding's Identity/Identity mapping, and 255..5000 samples per
+    ray, where |sigma delta| is small on both sides and the transmittance scan runs on 1 - a with a < 0.  Rays whose last sample
+    (interval 1e10 |d|) sits at a negative density, or whose transmittance exceeds 8, are left out (tests/parity_fuzz.py
+    IDENTITY_STATS); most cases must keep rays, and many must reach sigma delta <= -0.5."""
+    parity_fuzz.IDENTITY_STATS.clear()
+    for i in range(count):
+        desc = parity_fuzz.run_case(run_seed, i, kind, hip_device, "identity")
+        assert "mode=identity" in desc
+    stats = parity_fuzz.IDENTITY_STATS
+    used = [s for s in stats if s[0] > 0]
+    assert len(used) >= 0.75 * len(stats), stats
+    if kind != "long":  # (hundreds of samples per ray: |sigma delta| stays small by construction)
+        assert sum(s[2] <= -0.5 for s in used) >= 0.2 * len(used), stats

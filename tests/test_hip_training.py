@@ -12,7 +12,7 @@ from thr3ed_atom_amd import ops
 from thr3ed_atom_amd.optim import FlatGrid, FusedAdam
 from thr3ed_atom_amd.trainers import PosedImagesInMemory, TrainStepper, train_sh_vox_grid_vol_mod_with_posed_images
 from oracle import relu_field_oracle as orc
-from tests.helpers import hash_uniform, hotdog_like_camera, load_golden, procedural_grid, sparse_scene_grid
+from tests.helpers import hash_uniform, hotdog_like_camera, identity_regime, load_golden, procedural_grid, signed_density_grid, sparse_scene_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -537,12 +537,14 @@ def _binned_gradients(grid, rays, cfg, target, device, diffuse_too=True, accumul
 
 @pytest.mark.parametrize("accumulate,binning", [(False, "sort"), (True, "sort"), (False, "count"), (False, "fused"), (False, "merged"), (True, "merged")])
 @pytest.mark.parametrize("storage", ["reference", "split", "bricked"])
-@pytest.mark.parametrize("case", ["grid16_sh2", "aniso_sh2_abs", "aniso_sh1_softplus", "cube20_sh0", "aniso_sh3"])
+@pytest.mark.parametrize("case", ["grid16_sh2", "aniso_sh2_abs", "aniso_sh1_softplus", "cube20_sh0", "aniso_sh3", "aniso_sh2_identity"])
 def test_binned_backward_equals_atomic_backward(hip_device, storage, case, accumulate, binning):
     """The LDS-aggregated backward (emit -> 16-bit sort by (brick, flags) -> one workgroup per 8^3-node brick that owns
     its nodes exclusively -> plain coalesced stores) gives the gradient of the atomic scatter (and therefore of the reference)
     for specular + diffuse renders, including partial bricks, the grid border, SH degree 0-3 (degree 3 = four 16-channel
-    accumulator blocks per tile) and the abs / softplus density modes."""
+    accumulator blocks per tile) and the abs / softplus / identity density modes (identity: signed densities, negative occupancies and
+    transmittances above 1 -- both adjoints share the occupancy helper, so this is a consistency check; the oracle checks are in
+    tests/test_hip_parity.py)."""
     from thr3ed_atom_amd.voxels import unpack_split
 
     cam = hotdog_like_camera()
@@ -555,9 +557,16 @@ def test_binned_backward_equals_atomic_backward(hip_device, storage, case, accum
         "aniso_sh1_softplus": ((9, 17, 8), 12, "softplus", (0.3, 0.17, 0.35), (0.0, 0.0, 0.0), 5.0),
         "cube20_sh0": ((20, 20, 20), 3, "relu", (0.15,) * 3, (0.0, 0.0, 0.0), 100.0 / 3.0),
         "aniso_sh3": ((11, 17, 9), 48, "relu", (0.27, 0.17, 0.3), (0.0, 0.05, 0.0), 20.0),
+        "aniso_sh2_identity": ((13, 9, 18), 27, "identity", (0.22, 0.3, 0.16), (0.1, -0.05, 0.1), 5.0),
     }[case]
-    acts = {"relu": (torch.nn.Identity(), torch.nn.ReLU()), "softplus": (torch.nn.Identity(), torch.nn.Softplus()), "abs": (torch.abs, torch.nn.Identity())}[mode]
-    dens, feat = procedural_grid(dims, F, 303)
+    acts = {"relu": (torch.nn.Identity(), torch.nn.ReLU()), "softplus": (torch.nn.Identity(), torch.nn.Softplus()), "abs": (torch.abs, torch.nn.Identity()),
+            "identity": (torch.nn.Identity(), torch.nn.Identity())}[mode]
+    dens, feat = signed_density_grid(dims, F, 303) if mode == "identity" else procedural_grid(dims, F, 303)
+    if mode == "identity":  # the regime is covered (sigma delta <= -0.5), and no ray's 1e10-long last interval has a negative density
+        r64 = orc.render(dens.double(), feat.double(), T(g7["origins"]).double(), T(g7["directions"]).double(), orc.make_aabb(dims, voxel, loc), cam["near"],
+                         cam["far"], 40, rho, mode, white_bkgd=True)
+        xmin, _, usable = identity_regime(r64["processed"], r64["deltas"])
+        assert float(xmin.min()) <= -0.5 and bool(usable.all())
     grid = rf.VoxelGrid(dens.to(hip_device), feat.to(hip_device), rf.VoxelSize(*voxel), rf.VoxelGridLocation(*loc), density_preactivation=acts[0],
                         density_postactivation=acts[1], expected_density_scale=rho, tunable=True, storage=storage)
     cfg = rf.SHVoxGridRenderConfig(40, rf.CameraBounds(cam["near"], cam["far"]), perturb_sampled_points=False, white_bkgd=True)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import relu_field_oracle as orc
-from tests.helpers import hash_uniform, load_golden, procedural_grid
+from tests.helpers import hash_uniform, identity_regime, load_golden, procedural_grid, signed_density_grid
 
 
 def T(a):
@@ -245,6 +245,46 @@ def test_g13_last_sample_inside_the_volume(mode):
     # the regime is real: every ray ENDS inside the box
     end = T(g["origins"]) + float(g["far"]) * T(g["directions"])
     assert bool((end.abs() < 1.5).all())
+
+
+G15_CASES = [("white", {}), ("black", {"white_bkgd": False}), ("jitter", {"t_rand": True})]
+
+
+def g15_render_kwargs(g, over):
+    """the oracle's arguments for render configuration `over` of golden G15 (identity densities; oracle/gen_golden.py)"""
+    kw = dict(origins=T(g["origins"]), directions=T(g["directions"]), aabb=orc.make_aabb((12, 12, 12), (3.0 / 12,) * 3), near=float(g["near"]),
+              far=float(g["far"]), num_samples=48, density_scale=float(g["rho"]), density_mode="identity", white_bkgd=True)
+    kw.update(over)
+    if over.get("t_rand"):
+        kw["t_rand"] = T(g["t_rand"])
+    return kw
+
+
+@pytest.mark.parametrize("tag,over", G15_CASES, ids=[c[0] for c in G15_CASES])
+def test_g15_identity_density(tag, over):
+    """Identity/Identity densities: sigma is signed, alpha = 1 - exp(-sigma delta) is negative in the field's pockets and the
+    transmittance grows above 1.  The oracle against the reference's own output (what the HIP tests of the mode lean on)."""
+    g = load_golden("g15_identity_density.npz")
+    dens, feat = signed_density_grid((12, 12, 12), 27, 151)
+    out, loss, gd, gf = _l1_grads(dens, feat, g15_render_kwargs(g, over), T(g["target"]))
+    assert torch.equal(out["colour"], T(g[f"{tag}_colour"])) and torch.equal(out["depth"], T(g[f"{tag}_depth"])) and torch.equal(out["acc"], T(g[f"{tag}_acc"]))
+    assert loss.item() == float(g[f"{tag}_loss"])
+    np.testing.assert_allclose(gd.numpy(), g[f"{tag}_gd"], rtol=1e-4, atol=1e-8)
+    np.testing.assert_allclose(gf.numpy(), g[f"{tag}_gf"], rtol=1e-4, atol=1e-8)
+    # the regime is real: sigma delta of -1 and below, a transmittance above 2 (and below 8), no ray whose 1e10-long last interval
+    # has a negative density
+    xmin, tmax, usable = identity_regime(out["processed"], out["deltas"])
+    assert float(xmin.min()) <= -1.0 and 2.0 < float(tmax.max()) < 8.0 and bool(usable.all())
+
+
+def test_g15_voxel_grid_forward_identity_bit_exact():
+    """VoxelGrid.forward in identity mode (signed densities) on G3's anisotropic grid and points, stored by golden G15."""
+    g3, g = load_golden("g3_voxel_grid.npz"), load_golden("g15_identity_density.npz")
+    dens, feat = procedural_grid((5, 6, 7), 27, 31)
+    aabb = orc.make_aabb((5, 6, 7), tuple(g3["aniso_voxel"]), tuple(g3["aniso_loc"]))
+    out = orc.voxel_grid_forward(dens, feat, T(g3["aniso_points"]), aabb, float(g3["aniso_rho"]), "identity")
+    assert torch.equal(out, T(g["aniso_identity"]))
+    assert float(out[:, -1].min()) < 0.0 < float(out[:, -1].max())
 
 
 NOISE_CASES = [("relu", "relu", {}), ("relu_diffuse_black", "relu", {"render_diffuse": True, "white_bkgd": False}), ("softplus", "softplus", {})]

@@ -270,21 +270,24 @@ __device__ __forceinline__ float wave_sum(float x) {
 // own CPU (SLEEF) and GPU (libdevice) paths differ from each other by as much; the parity bar is 1e-5.
 __device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 __device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_fast(-x)); }
-// alpha = 1 - exp(-x), x = sigma * delta >= 0 (density2occupancy_pb, accumulate.py:24-28), the way the REFERENCE's float32 arithmetic
+// alpha = 1 - exp(-x), x = sigma * delta (density2occupancy_pb, accumulate.py:24-28; x < 0 only under Identity/Identity densities, where
+// alpha < 0 and the transmittance grows above 1), the way the REFERENCE's float32 arithmetic
 // produces it: E = exp(-x) correctly rounded, alpha = 1 - E (an exact subtraction: alpha is a multiple of 2^-24 and 1 - alpha == E, so
 // that weights alpha_i T_i and transmittances T_i E_i telescope without a bias).  v_exp_f32 is a one-ulp exponential: at the small x of
 // densely sampled rays (1000+ samples: x ~ 1e-3) its errors in E near 1 showed as 3..8e-5 on depth at 4000 .. 5000 samples per ray, where the
 // float32 reference stays within 2e-6 of the float64 value (tests/parity_fuzz.py, kind "long").  Below 1/16: E = 1 - (x - x^2/2 + ... ),
 // the series to 2e-9 relative, i.e. the correctly rounded exponential in all but a handful of cases.  (alpha taken from the series
 // itself is MORE accurate than the reference's -- and then 1 - alpha is rounded, with the same sign sample after sample where the
-// density varies slowly: accumulated weights of opaque rays came out 1.5e-5 short of 1.  Measured, not kept.)
+// density varies slowly: accumulated weights of opaque rays came out 1.5e-5 short of 1.  Measured, not kept.)  The series is taken for
+// |x| < 1/16 only: truncated, it falls away from exp(-x) fast on the negative side (1.4e-5 relative at x = -0.5, 0.93 at x = -10), and
+// exp_fast is right for either sign (+inf for a negative density over the last sample's 1e10-long interval, as in the reference).
 __device__ __forceinline__ float occupancy_alpha(float x, float& E) {
   float t = __builtin_fmaf(-x, 1.0f / 120.0f, 1.0f / 24.0f);
   t = __builtin_fmaf(-x, t, 1.0f / 6.0f);
   t = __builtin_fmaf(-x, t, 0.5f);
   t = __builtin_fmaf(-x, t, 1.0f);
   const float big = exp_fast(-x);
-  E = (x < 0.0625f) ? __builtin_fmaf(-x, t, 1.0f) : big;
+  E = (__builtin_fabsf(x) < 0.0625f) ? __builtin_fmaf(-x, t, 1.0f) : big;
   return 1.0f - E;
 }
 // softplus'(x) = sigmoid(x) = 1 - exp(-softplus(x)), from the cached activated density s = softplus(x) >= 0, to RELATIVE accuracy: a
