@@ -382,6 +382,24 @@ int rf_upsample_grid(const RFGrid* src, const RFGrid* dst, void* stream);
  * Parameters (thre3d_reprs/voxels.py:70-71) can keep an RF_LAYOUT_SPLIT shadow of them for the forward passes this way. */
 int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream);
 
+/* Iso-surface extraction (csrc/mesh_kernels.hip; the contract -- field, lattice, Kuhn tetrahedra, edge keys, orientation and
+ * canonical order -- is in that file's header and in DESIGN.md).  The level set sigma = iso_level of the grid's density on the
+ * lattice of `subdivisions` (1..8) points per voxel and axis plus one guard plane on each AABB face, as a closed oriented mesh.
+ * Three steps: rf_mesh_tiles (host only) gives the number of tiles nt of the lattice; rf_mesh_count writes the vertex counts
+ * of the tiles to counts_dev[0 : nt] and their triangle counts to counts_dev[nt : 2 nt] (int64); the caller turns both rows into
+ * exclusive prefix sums (offsets_dev, same shape) and allocates V = sum of row 0 vertices, T = sum of row 1 triangles;
+ * rf_mesh_emit writes, in canonical order, edge_keys_dev [V] (int64, ascending), positions_dev [V,3], colours_dev [V,3] and
+ * normals_dev [V,3] (both optional: NULL skips them) and face_edges_dev [T,3] (the edge keys of each triangle's vertices: their
+ * positions in edge_keys_dev are the vertex indices).  Only the density and the three degree-0 coefficients are read.
+ * RF_ERR_NULL_POINTER / RF_ERR_BAD_SHAPE (dims, subdivisions outside [1, 8], a non-finite iso_level) before any device access;
+ * rf_mesh_tiles returns the code instead of a count.  (Added to ABI version 4 compatibly: no existing struct or signature
+ * changed.) */
+int64_t rf_mesh_tiles(const RFGrid* grid, int32_t subdivisions);
+int rf_mesh_count(const RFGrid* grid, int32_t subdivisions, float iso_level, int64_t* counts_dev, void* stream);
+int rf_mesh_emit(const RFGrid* grid, int32_t subdivisions, float iso_level, const int64_t* offsets_dev, int64_t num_vertices,
+                 int64_t num_faces, int64_t* edge_keys_dev, float* positions_dev, float* colours_dev, float* normals_dev,
+                 int64_t* face_edges_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

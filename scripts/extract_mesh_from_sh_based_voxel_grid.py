@@ -1,0 +1,52 @@
+#!/usr/bin/env python
+"""Extract the geometry of a trained model as a coloured, closed triangle mesh (binary PLY) -- the iso-surface sigma = iso_level
+of the ReLU field sampled at sub-voxel resolution on the GPU (thr3ed_atom_amd.mesh).  Checkpoints written by this build OR by the
+reference load (create_volumetric_model_from_saved_model maps the reference's pickled names).
+
+    python scripts/extract_mesh_from_sh_based_voxel_grid.py -i out/saved_models/model_final.pth -o mesh.ply --subdivisions 2
+"""
+import math
+import os
+import sys
+import time
+
+import click
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import thr3ed_atom_amd as rf  # noqa: E402
+
+
+# fmt: off
+@click.command()
+# Required arguments:
+@click.option("-i", "--model_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="path to the trained (reconstructed) model")
+@click.option("-o", "--output_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="path of the .ply file to write")
+# Non-required extraction options:
+@click.option("--iso_level", type=click.FLOAT, default=None, required=False,
+              help="density of the surface; default ln 2 / min(voxel_size): a one-voxel slab at that density is 50 % opaque")
+@click.option("--subdivisions", type=click.IntRange(min=1, max=8), default=2, required=False, help="lattice points per voxel and axis (sub-voxel surfaces of the ReLU field)")
+# fmt: on
+def main(**kwargs) -> None:
+    config = dict(kwargs)
+    dev = torch.device("cuda:0")
+    creator = lambda info: rf.create_voxel_grid_from_saved_info_dict(info, storage="split")  # noqa: E731
+    model, _ = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)
+    grid = model.thre3d_repr
+    iso = config["iso_level"]
+    if iso is None:
+        iso = math.log(2.0) / min(grid._voxel_size)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mesh = rf.extract_mesh(grid, iso, subdivisions=config["subdivisions"])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    out_dir = os.path.dirname(os.path.abspath(config["output_path"]))
+    os.makedirs(out_dir, exist_ok=True)
+    rf.write_ply(mesh, config["output_path"])
+    print(f"grid {grid.grid_dims}, iso_level {iso:.6g}, subdivisions {config['subdivisions']}: V = {len(mesh.vertices)}, T = {len(mesh.faces)} "
+          f"in {1e3 * dt:.1f} ms (extraction incl. host synchronisation) -> {config['output_path']}")
+
+
+if __name__ == "__main__":
+    main()

@@ -43,5 +43,6 @@ from .composable import (  # noqa: F401  (the path at the granularity of the ref
     sample_aabb_bound_uniform_points_on_rays,
     sample_uniform_points_on_rays,
 )
+from .mesh import Mesh, extract_mesh, write_ply  # noqa: F401
 
 __version__ = "0.1.0"

@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "mesh_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -71,6 +71,9 @@ EXPORTED_SYMBOLS = [
     "rf_l1_loss_grad_pair",
     "rf_bin_offsets_pair",
     "rf_render_backward_emit_direct_pair",
+    "rf_mesh_tiles",
+    "rf_mesh_count",
+    "rf_mesh_emit",
 ]
 
 
@@ -308,9 +311,13 @@ def load() -> C.CDLL:
     lib.rf_l1_loss_grad_pair.argtypes = [C.POINTER(vp), vp, i64, f32, C.POINTER(vp), vp, vp, vp]
     lib.rf_bin_offsets_pair.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp]
     lib.rf_render_backward_emit_direct_pair.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), C.POINTER(u32), C.POINTER(RFPassScratch), vp]
+    # iso-surface extraction (csrc/mesh_kernels.hip)
+    lib.rf_mesh_tiles.argtypes = [C.POINTER(RFGrid), i32]
+    lib.rf_mesh_count.argtypes = [C.POINTER(RFGrid), i32, f32, vp, vp]
+    lib.rf_mesh_emit.argtypes = [C.POINTER(RFGrid), i32, f32, vp, i64, i64, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
-            getattr(lib, name).restype = C.c_int64 if name == "rf_brick_split_scratch_bytes" else C.c_int
+            getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles") else C.c_int
     if lib.rf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {lib.rf_abi_version()} != {ABI_VERSION} (stale build? run __graft_entry__.build())")
     lib.rf_abi_struct_size.argtypes = [C.c_int]
