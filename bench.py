@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (+ what the last timed step returned, as DIR/<name>.npy: two builds compare
                                                             output for output; the inputs are seeded, the same on every run)
+    python bench.py ... --full                             (+ the reporting legs listed under "With --full" below)
 
 Workload (BASELINE.json: "ray-samples/sec (fwd+bwd) ... 800x800 @ 128^3 grid", configs[2]/[3]):
 one STEP = one training iteration of the posed-image trainer on a 128^3 SH-degree-2 ReLU field -- a random 16384-ray batch
@@ -12,15 +13,20 @@ over RCCL when N > 1], Adam -- with 256 stratified (jittered) samples per ray.  
 whole job = N * 2 renders * 16384 rays * 256 samples * K / time, inputs resident in HBM, nothing skipped.
 Weak scaling: every rank draws its own 16384-ray batch.
 
-Also in the same JSON line:
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line.  Also in that line,
+from the timed steps themselves:
   roofline      the dominant kernel of the step: HIP events recorded by the library INSIDE the timed region (rf_train_step's
                 timing_events, on the launch stream); ``frac`` = HBM bytes from the PMC counters (profiles/pmc_traffic.json,
                 rocprofv3 --pmc passes of this command) / this run's kernel time / 8 TB/s; ``frac_processed`` = the algorithmic
                 bytes of SURVEY 8d on the units the launch REALLY processes (records emitted, counted on the device) -- never the
                 nominal in-AABB count a kernel legitimately skips most of;
+
+With --full (a leg whose own option is given a count runs without it too; a leg that does not run is null in the line):
   fwd_render    configs[1], full 800x800 frame (one launch), on the init field and on a semi-transparent field where every
                 ray traverses the whole volume;
   highres_render configs[4]; strict_dropin = the torch.autograd.Function path a reference user gets;
+  train_256     the same iteration at the reference CLI's final stage (256^3, 512 samples);
+  ms_per_step_windows, second_weak_scaling_point   more windows of K steps behind the official one; the step on a larger batch;
   cpu_baseline  the oracle (checker only) timed on the host cores.
 """
 import argparse
@@ -707,7 +713,12 @@ def run_guarded(fn, timeout_s, dev):
     return box.get("result"), None
 
 
-def main():
+# the reporting legs behind the headline: their sizes under --full.  A plain run skips every one whose option is not given; none of them
+# changes what the timed steps compute (the legs in front of the training draw from torch's generator before it is re-seeded for the steps).
+FULL_LEGS = {"render_frames": 5, "highres_frames": 5, "dropin_steps": 20, "windows": 9, "second_point_rays": 32768, "train256_steps": 10, "cpu_rays": 2048}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -718,13 +729,16 @@ def main():
     ap.add_argument("--samples", type=int, default=256)
     ap.add_argument("--image-size", type=int, default=800)
     ap.add_argument("--images", type=int, default=8)
-    ap.add_argument("--render-frames", type=int, default=5, help="full-frame forward renders timed for fwd_render (0 = skip)")
-    ap.add_argument("--highres-frames", type=int, default=5, help="frames timed for the 256^3 / 512-sample configs[4] render (0 = skip)")
-    ap.add_argument("--cpu-rays", type=int, default=2048, help="rays of the cpu_baseline training sample (0 = skip the CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the reporting legs behind the headline (fwd_render, highres_render, strict_dropin, train_256, cpu_baseline, "
+                    "ms_per_step_windows, second_weak_scaling_point) at the sizes in brackets below; without it they are skipped unless given a count")
+    ap.add_argument("--render-frames", type=int, default=None, help="full-frame forward renders timed for fwd_render (0 = skip) [--full: 5]")
+    ap.add_argument("--highres-frames", type=int, default=None, help="frames timed for the 256^3 / 512-sample configs[4] render (0 = skip) [--full: 5]")
+    ap.add_argument("--cpu-rays", type=int, default=None, help="rays of the cpu_baseline training sample (0 = skip the CPU baseline) [--full: 2048]")
     ap.add_argument("--cpu-full-rays", type=int, default=16384, help="rays of the cpu_baseline's full training batch (SURVEY 8d cfg3; one timed step, ~20 s; 0 = skip)")
     ap.add_argument("--cpu-fwd-rays", type=int, default=32768, help="rays of the cpu_baseline forward-only chunk (SURVEY 8d: one parallel_rays_chunk_size chunk)")
-    ap.add_argument("--train256-steps", type=int, default=10, help="steps timed for the train_256 leg: the iteration at the reference CLI's final stage, 256^3 / 512 samples (0 = skip)")
-    ap.add_argument("--dropin-steps", type=int, default=20, help="steps timed for the strict drop-in configuration (0 = skip)")
+    ap.add_argument("--train256-steps", type=int, default=None, help="steps timed for the train_256 leg: the iteration at the reference CLI's final stage, 256^3 / 512 samples (0 = skip) [--full: 10]")
+    ap.add_argument("--dropin-steps", type=int, default=None, help="steps timed for the strict drop-in configuration (0 = skip) [--full: 20]")
     ap.add_argument("--storage", choices=["split", "bricked", "reference"], default="split",
                     help="HBM layout of the grid: split = MI355X-native (what the trainer uses), reference = the reference's two tensors")
     ap.add_argument("--ray-selection", choices=["keyed", "randperm"], default="keyed",
@@ -740,14 +754,22 @@ def main():
                     help="data-parallel exchange: owner = owner-computes (record slices all-to-all -> merged brick pass + Adam on the rank's own bricks -> "
                     "parameter all-gather), dense = reduce-scatter of the gradient bucket -> sharded Adam -> all-gather")
     ap.add_argument("--timed-steps", type=int, default=5, help="how many of the --steps record per-kernel HIP events")
-    ap.add_argument("--second-point-rays", type=int, default=32768, help="rays per GPU of the second weak-scaling point timed behind the windows (0 = skip)")
-    ap.add_argument("--windows", type=int, default=9, help="further windows of --steps steps timed behind the official one (ms_per_step_windows)")
+    ap.add_argument("--second-point-rays", type=int, default=None, help="rays per GPU of the second weak-scaling point timed behind the windows (0 = skip) [--full: 32768]")
+    ap.add_argument("--windows", type=int, default=None, help="further windows of --steps steps timed behind the official one (ms_per_step_windows) [--full: 9]")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads for cpu_baseline (0 = the cgroup CPU quota, at most 64)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them returned (its StepStats: losses and MSEs) to DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         raise SystemExit("--steps must be at least 1")
+    for name, full_size in FULL_LEGS.items():
+        if getattr(args, name) is None:
+            setattr(args, name, full_size if args.full else 0)
+    return args
+
+
+def main():
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         respawn_under_torchrun(args.gpus)  # does not return

@@ -133,7 +133,7 @@ def test_bench_line_contract(hip_device):
     than the synchronised frame call that contains it."""
     import json
 
-    r = _run([os.path.join(REPO_ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--cpu-rays", "256", "--cpu-fwd-rays", "512",
+    r = _run([os.path.join(REPO_ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full", "--cpu-rays", "256", "--cpu-fwd-rays", "512",
               "--render-frames", "1", "--highres-frames", "0", "--dropin-steps", "2", "--second-point-rays", "20000"], timeout=900)
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -170,6 +170,23 @@ def test_bench_line_contract(hip_device):
     assert cpu["kind"] == "port" and cpu["unit"] == "ray-samples/s" and cpu["value"] > 0 and cpu["cores"] >= 1 and "sample" in cpu
     assert cpu["cfg1_full_frame"]["max_abs_colour_difference_gpu_vs_cpu"] <= 1e-5
     assert line["fwd_render"]["init_field"]["render_launches_per_frame"] == 1
+
+
+def test_bench_plain_run_skips_the_reporting_legs(hip_device):
+    """bench.py without --full (small workload): the headline and what its timed steps recorded (per-kernel events, the roofline priced
+    on them), and none of the reporting legs -- each is null in the line."""
+    import json
+
+    r = _run([os.path.join(REPO_ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--grid", "64", "--rays", "4096", "--samples", "64",
+              "--image-size", "200"], timeout=900)
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-1500:], r.stderr[-3000:])
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["higher_is_better"] is True and line["dtype"] == "f32"
+    np.testing.assert_allclose(line["value"], 2 * 4096 * 64 / (line["ms_per_step"] * 1e-3), rtol=1e-6)
+    assert line["kernels"] and line["roofline"] is not None
+    for leg in ("fwd_render", "highres_render", "strict_dropin", "train_256", "cpu_baseline", "ms_per_step_windows", "second_weak_scaling_point"):
+        assert line[leg] is None, leg
 
 
 def test_bench_dump_outputs(hip_device, tmp_path):

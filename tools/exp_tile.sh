@@ -1,6 +1,6 @@
 # Frame render A/B (GPU box, repo root): the ray-packet kernel (RF_FRAME_TILES=1 forces it) against the per-ray kernel (=0), configs[1] and configs[4].
 run() {
-  RF_FRAME_TILES=$1 python bench.py --steps 3 --warmup 2 --cpu-rays 0 --dropin-steps 0 --windows 0 --second-point-rays 0 2>/dev/null | python -c "
+  RF_FRAME_TILES=$1 python bench.py --full --steps 3 --warmup 2 --cpu-rays 0 --dropin-steps 0 --windows 0 --second-point-rays 0 2>/dev/null | python -c "
 import json,sys
 l=json.loads([x for x in sys.stdin if x.startswith('{')][0])
 f=l['fwd_render']; h=l['highres_render']

@@ -3,7 +3,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared -I i
 for w in 3 4; do
   /opt/rocm/bin/hipcc $FLAGS -DRF_TILE_WAVES=$w -o tools/exp_tile_w$w.so || exit 1
   for rep in 1 2; do
-  RF_FRAME_TILES=1 RF_LIB_PATH=$PWD/tools/exp_tile_w$w.so python bench.py --steps 3 --warmup 2 --cpu-rays 0 --dropin-steps 0 --windows 0 --second-point-rays 0 --highres-frames 3 2>/dev/null | python -c "
+  RF_FRAME_TILES=1 RF_LIB_PATH=$PWD/tools/exp_tile_w$w.so python bench.py --full --steps 3 --warmup 2 --cpu-rays 0 --dropin-steps 0 --windows 0 --second-point-rays 0 --highres-frames 3 2>/dev/null | python -c "
 import json,sys
 l=json.loads([x for x in sys.stdin if x.startswith('{')][0])
 f=l['fwd_render']; h=l['highres_render']

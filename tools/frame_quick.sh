@@ -4,7 +4,7 @@ ROOT=$PWD
 TAG=${1:-fq}
 OUT=$ROOT/gpurun_out/fq_$TAG
 rm -rf $OUT; mkdir -p $OUT
-ARGS="--steps 1 --warmup 0 --cpu-rays 0 --dropin-steps 0 --render-frames 5 --images 1"
+ARGS="--full --steps 1 --warmup 0 --cpu-rays 0 --dropin-steps 0 --render-frames 5 --images 1"
 python $ROOT/bench.py $ARGS > $OUT/line.json 2> $OUT/line.err
 cd /tmp
 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_INSTS_SALU GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/p1 -- python $ROOT/bench.py $ARGS --highres-frames 0 --render-frames 1 > /dev/null 2> $OUT/p1.err
