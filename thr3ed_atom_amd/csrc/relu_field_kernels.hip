@@ -2757,6 +2757,9 @@ __device__ __forceinline__ void lds_request_u8(uint32_t& v, uint32_t addr) {
   asm volatile("ds_read_u8 %0, %1" : "+v"(v) : "v"(addr));
 }
 __device__ __forceinline__ void lds_wait(uint32_t& a, uint32_t& b) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b)); }
+__device__ __forceinline__ void lds_wait(float& a, float& b, float& c, float& d, uint32_t& f) {
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(f));
+}
 __device__ __forceinline__ void lds_wait(float& a, float& b, float& c, float& d, float& e, uint32_t& f) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
 }
@@ -2793,6 +2796,12 @@ __host__ __device__ inline int gather_lds_words(int B, int C, int BX = 8) {
 // records -- 16 tiles, four per wave as in the 8^3 case, half the LDS: FOUR workgroups per CU instead of two.  The pass is bound by the
 // latencies of a workgroup's serial phases (ranges -> first records -> tile loops -> flush), and twice the workgroups hide twice as
 // many of them; the price is one more brick face across x (a record is read 1.58 x instead of 1.42 x) and twice the keys.
+// SEP (BX = 4, K = 9, one workgroup per brick): the base-channel records of render_diffuse passes are summed SEPARABLY.  Their trilinear
+// weight is wx * wy * wz and the brick has exactly 4 x-planes, so for each 4 x 4 (y, z) block of the 8 x 8 yz face one 16 x 16
+// accumulator N[(c, x)][(y, z)] takes them: A = g_c(record) * wx(record, x), B = wy(record, y) * wz(record, z), four records per
+// v_mfma_f32_16x16x4_f32.  Wave w owns block w and ONE list of the records that touch it (1.56 blocks per record against 2.81 tiles;
+// every B column useful, where the tile form fed zeros to 12 of 16).  The blocks are added to channels 0..3 of the image after the
+// wide tiles: those channels are (sum of the full-width records) + (sum of the base-channel records).
 template <int K, bool ADAM, bool ONE_ROUND = false, bool SPLIT = false, int BX = 8, bool MIRROR = false>
 __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9 ? 2 : 4)) void brick_gather_kernel(GridArgs g, BrickArgs a, float* gdens, float* gfeat) {
   static_assert(BX == 8 || (BX == 4 && ONE_ROUND && !SPLIT), "4 x 8 x 8 bricks: 8-node y and z edges, one workgroup per brick");
@@ -2808,10 +2817,11 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
   static_assert(NT == 1 || NT == 2 || NT == 4, "one, two or four 16-channel blocks (SH degree 0 / base lists, 1-2, 3)");
   constexpr int CS = C4;
   constexpr int NW = GB / 64;    // mask words per tile
+  constexpr bool SEP = BX == 4 && K == 9 && ONE_ROUND && !SPLIT;  // separable yz-block sums of the base-channel records (above)
   extern __shared__ __attribute__((aligned(16))) float acc[];  // first the batch buffers, in the end the accumulator image the flush reads
   float* rows = acc;                                            // [GB][RW] per-channel values of the batch's records
   float* wtab = acc + GB * gather_record_words(C4);   // [3][8][GROW]: axis, local node coordinate, record
-  __shared__ uint32_t s_tmask[GB];                   // record -> bit t: it touches tile t
+  __shared__ uint32_t s_tmask[GB];                   // record -> bit t: it touches tile t (SEP base-channel batches: yz-block t)
   __shared__ unsigned char s_list[4 * NWV][GB + 24];      // tile -> its records (+ padding of the last instructions, + read-ahead slack)
   __shared__ __attribute__((aligned(16))) int s_wstart[kMaxRangesKind], s_wcum[kMaxRangesKind + 8];  // ranges of the full-width lists: first record, running count
   __shared__ __attribute__((aligned(16))) int s_nstart[kMaxRangesKind], s_ncum[kMaxRangesKind + 8];  // ... of the base-channel lists of a mixed call
@@ -2888,6 +2898,9 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
   for (int tl = 0; tl < 4; ++tl)
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) accr[tl][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // SEP: yz-block `wave` of the base-channel records.  Accumulator register e of a lane: channel lane >> 4, x-plane e, (y, z) = the
+  // block's node lane & 15 (y: bits 2..3, z: bits 0..1)
+  f32x4 naccr = f32x4{0.f, 0.f, 0.f, 0.f};
 
   if (any) {
     const int nba = (total + GB - 1) / GB, nbd = (total_d + GB - 1) / GB;
@@ -2899,8 +2912,10 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     // thread of the record), and its row of per-channel values.  A full-width record of an SH grid arrives COMPACT -- d density,
     // d raw r, g, b and the unit viewing direction -- and is expanded here, d raw[colour] * Y_k(v) in the operation order of the
     // reference's evaluate_spherical_harmonics, so that the expanded values never exist in HBM.
-    auto stage = [&](auto expand_tag, float4 q0, float4 q1, float4 q2, int nrec) {
+    // (BLOCKS: a base-channel batch of the SEP form -- the mask holds the yz-blocks the record touches, bit 2 * (y >> 2) + (z >> 2))
+    auto stage = [&](auto expand_tag, auto blocks_tag, float4 q0, float4 q1, float4 q2, int nrec) {
       constexpr bool EXPAND = decltype(expand_tag)::value;
+      constexpr bool BLOCKS = decltype(blocks_tag)::value;
       constexpr int RW = gather_record_words(EXPAND ? C4 : 4);
       if (half == 0) {
         uint32_t tm = 0, wnow = 0x00ffffffu;
@@ -2922,7 +2937,7 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
           for (int ax = 0; ax < 3; ++ax) {
             const float fl = floorf(idx[ax]);
             const int c = (int)fl - org[ax];  // lower node of the cell relative to the brick: -1 .. B - 1
-            const int sh = ax == 2 ? 2 : 1;
+            const int sh = (BLOCKS && ax > 0) || ax == 2 ? 2 : 1;
             uint32_t bits = 0;
             if (c >= 0) {
               wcol[(ax * 8 + c) * GROW] = (fl + 1.0f) - idx[ax];  // same arithmetic as locate()
@@ -2935,13 +2950,17 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
             pb[ax] = bits;
             wnow |= (uint32_t)(c + 1) << (8 * ax);
           }
-          uint32_t yz = 0;
+          if constexpr (BLOCKS) {
+            if (pb[0]) tm = ((pb[1] & 1u) ? pb[2] : 0u) | ((pb[1] & 2u) ? pb[2] << 2 : 0u);
+          } else {
+            uint32_t yz = 0;
 #pragma unroll
-          for (int py = 0; py < 4; ++py)
-            if ((pb[1] >> py) & 1u) yz |= pb[2] << (py * npz);
+            for (int py = 0; py < 4; ++py)
+              if ((pb[1] >> py) & 1u) yz |= pb[2] << (py * npz);
 #pragma unroll
-          for (int px = 0; px < 4; ++px)
-            if ((pb[0] >> px) & 1u) tm |= yz << (px * npy * npz);
+            for (int px = 0; px < 4; ++px)
+              if ((pb[0] >> px) & 1u) tm |= yz << (px * npy * npz);
+          }
         }
         wprev = wnow;
         s_tmask[rec_id] = tm;
@@ -3076,6 +3095,76 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
       __syncthreads();
       RF_PROF_MARK(2);
     };
+    // -- SEP: the base-channel batch into the yz-block accumulators.  One list per wave (the records that touch its block, in
+    // record order), then the same two-deep pipeline of LDS requests as the tile loop: four reads per lane and instruction (g, wx,
+    // wy, wz), the products formed in registers
+    auto process_blocks = [&](int nrec) {
+      constexpr int RW = gather_record_words(4);
+      RF_PROF_MARK(7);
+      __syncthreads();
+      RF_PROF_MARK(2);
+#if defined(RF_BRICK_PROFILE) || defined(RF_BRICK_ABLATE)
+      const bool no_lists = a.stagger & 0x200000, no_tiles = a.stagger & 0x100000;
+#else
+      constexpr bool no_lists = false, no_tiles = false;
+#endif
+      unsigned char* list = s_list[wave];
+      int n = 0;
+      if (!no_lists)
+#pragma unroll
+        for (int wd = 0; wd < NW; ++wd) {
+          if (wd * 64 >= nrec) break;
+          const bool hit = (s_tmask[wd * 64 + lane] >> wave) & 1u;
+          const unsigned long long m = __ballot(hit);
+          const int pos = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+          if (hit) list[pos] = (unsigned char)(wd * 64 + lane);
+          n += __popcll(m);
+        }
+      if (lane < 8) list[n + lane] = 0;  // pad the last instructions with a record that exists
+      if (n > 0 && !no_tiles) {
+        // A row (c, x) = (mi >> 2, mi & 3); B column (y, z) = (4 (wave >> 1) + (jj >> 2), 4 (wave & 1) + (jj & 3))
+        const uint32_t a_list = lds_offset(list) + kk;
+        const uint32_t a_x = lds_offset(wtab + (mi & 3) * GROW);
+        const uint32_t a_y = lds_offset(wtab + (8 + 4 * (wave >> 1) + (jj >> 2)) * GROW);
+        const uint32_t a_z = lds_offset(wtab + (16 + 4 * (wave & 1) + (jj & 3)) * GROW);
+        const uint32_t a_g = lds_offset(rows + (mi >> 2));
+        const int nq = (n + 3) >> 2;
+        uint32_t ra = 0, rb = 0;
+        float xa = 0.f, ya = 0.f, za = 0.f, ga = 0.f, xb = 0.f, yb = 0.f, zb = 0.f, gb = 0.f;  // (sets A, B)
+        auto request_ops = [&](float& wx, float& wy, float& wz, float& g, uint32_t r) {
+          lds_request_f32<0>(wx, a_x + 4 * r);
+          lds_request_f32<0>(wy, a_y + 4 * r);
+          lds_request_f32<0>(wz, a_z + 4 * r);
+          lds_request_f32<0>(g, a_g + (uint32_t)__umul24(r, RW * 4));
+        };
+        auto multiply = [&](float wx, float wy, float wz, float g, int q) {
+          const float av = g * wx;
+          const float aa = (4 * q + kk < n) ? av : 0.0f;
+          naccr = __builtin_amdgcn_mfma_f32_16x16x4f32(aa, wy * wz, naccr, 0, 0, 0);
+        };
+        lds_request_u8(ra, a_list);
+        lds_request_u8(rb, a_list + 4);
+        lds_wait(ra, rb);
+        request_ops(xa, ya, za, ga, ra);
+        for (int q = 0; q < nq; q += 2) {
+          lds_wait(xa, ya, za, ga, rb);
+          lds_request_u8(ra, a_list + 4 * q + 8);
+          request_ops(xb, yb, zb, gb, rb);
+          multiply(xa, ya, za, ga, q);
+          if (q + 1 < nq) {
+            lds_wait(xb, yb, zb, gb, ra);
+            lds_request_u8(rb, a_list + 4 * q + 12);
+            request_ops(xa, ya, za, ga, ra);
+            multiply(xb, yb, zb, gb, q + 1);
+          }
+        }
+        lds_wait(xa, ya, za, ga, ra);  // nothing of this block stays in flight
+        lds_wait(xb, yb, zb, gb, rb);
+      }
+      RF_PROF_MARK(3);
+      __syncthreads();
+      RF_PROF_MARK(2);
+    };
     using Yes = std::integral_constant<bool, true>;
     using No = std::integral_constant<bool, false>;
 
@@ -3137,9 +3226,9 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     for (int s = 0; s < nba; ++s) {
       const int nrec = min(GB, total - s * GB);
       if constexpr (K > 1)
-        stage(Yes{}, w0, w1, w2, nrec);
+        stage(Yes{}, No{}, w0, w1, w2, nrec);
       else
-        stage(No{}, w0, w1, w2, nrec);
+        stage(No{}, No{}, w0, w1, w2, nrec);
       RF_PROF_MARK(1);  // waiting for the batch's loads, record pass
       fetch_wide(min(s + 1, nba - 1));  // (the last batch again at the end: cheaper than a conditional)
       RF_PROF_MARK(6);  // issuing the next batch's loads
@@ -3147,11 +3236,14 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     }
     for (int sd = 0; sd < nbd; ++sd) {
       const int nrec = min(GB, total_d - sd * GB);
-      stage(No{}, d0, d1, d1, nrec);
+      stage(No{}, std::integral_constant<bool, SEP>{}, d0, d1, d1, nrec);
       RF_PROF_MARK(1);
       fetch_narrow(min(sd + 1, nbd - 1));
       RF_PROF_MARK(6);
-      process(No{}, nrec);
+      if constexpr (SEP)
+        process_blocks(nrec);
+      else
+        process(No{}, nrec);
     }
     // -- the accumulator image for the flush (the batch buffers are dead).  Accumulator register e of a lane: node row
     // 4 (lane >> 4) + e of the tile, channel 16 nt + (lane & 15)
@@ -3170,6 +3262,14 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
             if (ch < CS) acc[nx * SX + ny * SY + nz * CS + ch] = accr[tl][nt][e];
           }
         }
+      }
+    }
+    if constexpr (SEP) {
+      if (total_d > 0) {  // (uniform) the yz-blocks onto channels 0..3 of the full-width sums, one lane per (node, channel)
+        __syncthreads();
+        const int ny = 4 * (wave >> 1) + (jj >> 2), nz = 4 * (wave & 1) + (jj & 3);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e * SX + ny * SY + nz * CS + kk] += naccr[e];
       }
     }
     __syncthreads();

@@ -16,8 +16,8 @@ PROF = os.path.join(ROOT, "tools", "librelu_field_hip_prof.so")
 if sys.argv[1] == "build":
     from thr3ed_atom_amd import _lib
 
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + _lib.HIPCC_FLAGS + ["-DRF_BRICK_PROFILE", "-I", _lib.INCLUDE_DIR,
-          os.path.join(_lib.CSRC_DIR, "relu_field_kernels.hip"), "-o", PROF]
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + _lib.HIPCC_FLAGS + ["-DRF_BRICK_PROFILE", "-I", _lib.INCLUDE_DIR] + \
+          [os.path.join(_lib.CSRC_DIR, s) for s in _lib.SOURCES] + ["-o", PROF]
     subprocess.run(cmd, check=True)
     print("built", PROF)
     sys.exit(0)
