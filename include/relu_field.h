@@ -362,6 +362,22 @@ int rf_grid_query_backward(const RFGrid* grid, const float* points_dev, int64_t 
                            const float* grad_out_dev, float* grad_densities_dev, float* grad_features_dev,
                            void* stream);
 
+/* Its adjoint into the query points (the reference gets it from autograd: grid_sample's gradient with respect to its
+ * sampling grid, through the normalisation of voxels.py:214-223): grad_points_dev [M, 3] is WRITTEN (not accumulated) from
+ * grad_out_dev [M, F+1]; every layout and density mode, the density channel through its activation slope.  (Added to ABI
+ * version 4 without a version change: additive.) */
+int rf_grid_query_backward_points(const RFGrid* grid, const float* points_dev, int64_t num_points,
+                                  const float* grad_out_dev, float* grad_points_dev, void* stream);
+
+/* dL/d(origins), dL/d(directions) of rf_render_forward (the reference gets them from autograd through
+ * _ray_aabb_intersection of sample.py:71-184, grid_sample's grid gradient, the SH basis of utils/spherical_harmonics.py and
+ * the interval lengths of accumulate.py:50-55): grad_origins_dev / grad_directions_dev [N, 3] are WRITTEN (not accumulated;
+ * either may be NULL).  `fwd` holds the caches of the matching forward call.  One result per ray, no atomics: bitwise
+ * deterministic.  Rays generated in-kernel (RFRayBatch.camera != NULL) -> RF_ERR_UNSUPPORTED.  The jitter (t_rand) gets no
+ * gradient.  (Added to ABI version 4 without a version change: additive.) */
+int rf_render_backward_rays(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, const RFRenderOut* fwd,
+                            const RFRenderGrads* grads, float* grad_origins_dev, float* grad_directions_dev, void* stream);
+
 /* Exact empty-cell mask for RF_FLAG_OCCUPANCY_SKIP (BASELINE.json configs[4]):
  * bit (cx, cy, cz), cx in [0, X] etc., is set iff any of the (up to 8) grid nodes
  * (cx-1..cx, cy-1..cy, cz-1..cz) that exist has a raw density that can yield sigma != 0 under

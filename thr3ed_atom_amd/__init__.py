@@ -14,8 +14,10 @@ from .camera import (  # noqa: F401
     get_thre360_animation_poses,
     get_thre360_spiral_animation_poses,
     mse2psnr,
+    perturb_pose,
     pose_spherical,
     scale_camera_intrinsics,
+    so3_exp,
 )
 from .render_interface import (  # noqa: F401
     Rays,
@@ -44,5 +46,6 @@ from .composable import (  # noqa: F401  (the path at the granularity of the ref
     sample_uniform_points_on_rays,
 )
 from .mesh import Mesh, extract_mesh, write_ply  # noqa: F401
+from .pose_refinement import pose_error, refine_camera_pose  # noqa: F401
 
 __version__ = "0.1.0"

@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = [
     "rf_brick_split_scratch_bytes",
     "rf_grid_query",
     "rf_grid_query_backward",
+    "rf_grid_query_backward_points",
+    "rf_render_backward_rays",
     "rf_build_occupancy",
     "rf_upsample_grid",
     "rf_convert_grid",
@@ -301,6 +303,8 @@ def load() -> C.CDLL:
     lib.rf_train_step.argtypes = [C.POINTER(RFGrid), C.POINTER(RFTrainStep), vp]
     lib.rf_grid_query.argtypes = [C.POINTER(RFGrid), vp, i64, vp, vp]
     lib.rf_grid_query_backward.argtypes = [C.POINTER(RFGrid), vp, i64, vp, vp, vp, vp]
+    lib.rf_grid_query_backward_points.argtypes = [C.POINTER(RFGrid), vp, i64, vp, vp, vp]
+    lib.rf_render_backward_rays.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, C.POINTER(RFRenderOut), C.POINTER(RFRenderGrads), vp, vp, vp]
     lib.rf_upsample_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), vp]
     lib.rf_convert_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), vp]
     lib.rf_build_occupancy.argtypes = [C.POINTER(RFGrid), f32, vp, vp]

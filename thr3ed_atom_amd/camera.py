@@ -78,6 +78,36 @@ def pose_spherical(yaw: float, pitch: float, radius: float, device=torch.device(
     return CameraPose(rotation=c2w[:3, :3], translation=c2w[:3, 3:])
 
 
+def so3_exp(omega: Tensor) -> Tensor:
+    """Rotation matrix [3, 3] of the axis-angle vector ``omega`` [3] (Rodrigues: I + A K + B K^2, K = [omega]_x,
+    A = sin(theta) / theta, B = (1 - cos(theta)) / theta^2).  Differentiable, in the dtype and on the device of ``omega``;
+    below theta = 1e-3 A and B come from their Taylor series, so the gradient at omega = 0 is exact (dR/d omega = the
+    generators of so(3))."""
+    omega = torch.as_tensor(omega).reshape(3)
+    zero = torch.zeros((), dtype=omega.dtype, device=omega.device)
+    wx, wy, wz = omega[0], omega[1], omega[2]
+    K = torch.stack([torch.stack([zero, -wz, wy]), torch.stack([wz, zero, -wx]), torch.stack([-wy, wx, zero])])
+    t2 = (omega * omega).sum()
+    small = t2 < 1e-6
+    t2_safe = torch.where(small, torch.ones_like(t2), t2)
+    theta = torch.sqrt(t2_safe)
+    A = torch.where(small, 1.0 - t2 / 6.0 + t2 * t2 / 120.0, torch.sin(theta) / theta)
+    B = torch.where(small, 0.5 - t2 / 24.0 + t2 * t2 / 720.0, (1.0 - torch.cos(theta)) / t2_safe)
+    eye = torch.eye(3, dtype=omega.dtype, device=omega.device)
+    return eye + A * K + B * (K @ K)
+
+
+def perturb_pose(pose: CameraPose, omega, tau) -> CameraPose:
+    """The pose R = so3_exp(omega) R0, t = t0 + tau of an initial pose (R0, t0): a rotation about the world origin's axes applied
+    to the camera's orientation and a translation of its centre.  Differentiable w.r.t. ``omega`` [3] and ``tau`` [3]; the
+    result has the dtype / device of ``omega`` and ``t`` keeps the [3, 1] shape."""
+    omega = torch.as_tensor(omega)
+    tau = torch.as_tensor(tau, dtype=omega.dtype, device=omega.device)
+    R0 = torch.as_tensor(pose.rotation).to(omega.device, omega.dtype).reshape(3, 3)
+    t0 = torch.as_tensor(pose.translation).to(omega.device, omega.dtype).reshape(3, 1)
+    return CameraPose(rotation=so3_exp(omega) @ R0, translation=t0 + tau.reshape(3, 1))
+
+
 def get_thre360_animation_poses(hemispherical_radius: float, camera_pitch: float, num_poses: int):
     """Turn-table path (imaging_utils.py:199-209): num_poses-1 yaws in [0, 360)."""
     yaws = np.linspace(0, 360, num_poses)[:-1]

@@ -287,6 +287,29 @@ def render_backward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_
     _lib.check(rc, "rf_render_backward")
 
 
+def render_backward_rays_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_rand, num_samples: int, near: float, far: float, flags: int,
+                             caches, g_colour: Optional[Tensor], g_depth: Optional[Tensor], g_acc: Optional[Tensor], want_origins: bool = True,
+                             want_directions: bool = True) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """Enqueue rf_render_backward_rays: (dL/d(origins) [N,3], dL/d(directions) [N,3]) float32, WRITTEN by the kernel (None where not
+    wanted).  The grid is read the way the forward pass read it (a reference-storage grid through its split shadow)."""
+    lib = _lib.load()
+    dev = origins.device
+    n = origins.shape[0]
+    rf_grid = grid.forward_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
+    rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
+    grads = _lib.RFRenderGrads()
+    grads.grad_colour_dev, grads.grad_depth_dev, grads.grad_acc_dev = _ptr(g_colour), _ptr(g_depth), _ptr(g_acc)
+    cache, tcache, stop, cmask = caches
+    fwd = _lib.RFRenderOut()
+    fwd.sample_cache_dev, fwd.trans_cache_dev, fwd.stop_cache_dev, fwd.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
+    go = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_origins else None
+    gdir = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_directions else None
+    with _span(f"render_backward_rays[{_variant(grid, flags)}]", dev):
+        rc = lib.rf_render_backward_rays(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), _ptr(go), _ptr(gdir), _stream(dev))
+    _lib.check(rc, "rf_render_backward_rays")
+    return go, gdir
+
+
 NO_BRICK = 0x7FFF
 
 
@@ -617,6 +640,10 @@ class _ReluFieldRender(torch.autograd.Function):
         for t in (first, second):
             if t is not None:
                 _require_hip(t, "grid tensor")
+        # ray gradients (a learnable camera pose, say): the sample cache is written for them too; the key histogram and the binned
+        # adjoint stay tied to the grid gradient
+        need_rays = bool(ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        ctx.need_rays, ctx.ray_dtypes = need_rays, (origins.dtype, directions.dtype)
         origins = origins.detach().to(torch.float32).contiguous()
         directions = directions.detach().to(torch.float32).contiguous()
         n = origins.shape[0]
@@ -634,8 +661,8 @@ class _ReluFieldRender(torch.autograd.Function):
             nb = brick_counts(grid, brick_size)
             key_hist = _take_hist(origins.device, nb[0] * nb[1] * nb[2] * 8)
         colour, depth, acc, disparity, caches = render_forward_raw(
-            grid, origins, directions, keyed if keyed is not None else t_rand, int(num_samples), float(near), float(far), int(flags), bool(need_grad),
-            key_hist=key_hist, brick_size=brick_size,
+            grid, origins, directions, keyed if keyed is not None else t_rand, int(num_samples), float(near), float(far), int(flags),
+            bool(need_grad) or need_rays, key_hist=key_hist, brick_size=brick_size,
         )
         ctx.grid, ctx.flags, ctx.keyed, ctx.key_hist, ctx.brick_size = grid, int(flags), keyed, key_hist, brick_size
         ctx.num_samples, ctx.near, ctx.far = int(num_samples), float(near), float(far)
@@ -643,7 +670,7 @@ class _ReluFieldRender(torch.autograd.Function):
         ctx.has_second = second is not None
         ctx.need_grad = bool(need_grad)
         saved = [first] + ([second] if second is not None else []) + [origins, directions]
-        if need_grad:
+        if need_grad or need_rays:
             saved += list(caches)
         if t_rand is not None:
             saved.append(t_rand)
@@ -656,8 +683,34 @@ class _ReluFieldRender(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_colour, g_depth, g_acc, _g_disparity):
-        if not ctx.need_grad:
+        if not ctx.need_grad and not ctx.need_rays:
             return (None,) * 11
+        ret_d, ret_f = None, None
+        if ctx.need_grad:
+            ret_d, ret_f = _ReluFieldRender._grid_backward(ctx, g_colour, g_depth, g_acc)
+        g_o = g_dir = None
+        if ctx.need_rays:
+            saved = list(ctx.saved_tensors)
+            origins, directions, cache, tcache, stop, cmask = saved[1 + ctx.has_second : 7 + ctx.has_second]
+            t_rand = saved[7 + ctx.has_second] if ctx.has_rand else ctx.keyed
+
+            def prep(g):
+                return None if g is None else g.detach().to(torch.float32).contiguous()
+
+            want_o, want_d = bool(ctx.needs_input_grad[2]), bool(ctx.needs_input_grad[3])
+            if g_colour is None and g_depth is None and g_acc is None:
+                g_o = torch.zeros_like(origins) if want_o else None
+                g_dir = torch.zeros_like(directions) if want_d else None
+            else:
+                g_o, g_dir = render_backward_rays_raw(ctx.grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags,
+                                                      (cache, tcache, stop, cmask), prep(g_colour), prep(g_depth), prep(g_acc), want_o, want_d)
+            g_o = None if g_o is None else g_o.to(ctx.ray_dtypes[0])
+            g_dir = None if g_dir is None else g_dir.to(ctx.ray_dtypes[1])
+        return ret_d, ret_f, g_o, g_dir, None, None, None, None, None, None, None
+
+    @staticmethod
+    def _grid_backward(ctx, g_colour, g_depth, g_acc):
+        """The adjoint into the grid tensors (atomic or binned), exactly as before ray gradients existed."""
         saved = list(ctx.saved_tensors)
         first = saved.pop(0)
         second = saved.pop(0) if ctx.has_second else None
@@ -718,7 +771,7 @@ class _ReluFieldRender(torch.autograd.Function):
                 grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags, (cache, tcache, stop, cmask),
                 prep(g_colour), prep(g_depth), prep(g_acc), gd, gf,
             )
-        return ret_d, ret_f, None, None, None, None, None, None, None, None, None
+        return ret_d, ret_f
 
 
 class _ReluFieldRenderPair(torch.autograd.Function):
@@ -837,6 +890,7 @@ class _GridQuery(torch.autograd.Function):
     def forward(ctx, first, second, points, grid: VoxelGrid):
         lib = _lib.load()
         _require_hip(points, "points")
+        ctx.points_dtype = points.dtype
         points = points.detach().to(torch.float32).contiguous()
         m = points.shape[0]
         out = torch.empty((m, grid.num_features + 1), dtype=torch.float32, device=points.device)
@@ -854,26 +908,39 @@ class _GridQuery(torch.autograd.Function):
         second = saved.pop(0) if ctx.has_second else None
         points = saved[0]
         g_out = g_out.detach().to(torch.float32).contiguous()
-        gd = torch.zeros_like(first)
-        gf = None if second is None else torch.zeros_like(second)
         rf_grid = ctx.grid.to_rf_grid()
-        _lib.check(
-            lib.rf_grid_query_backward(C.byref(rf_grid), points.data_ptr(), points.shape[0], g_out.data_ptr(), gd.data_ptr(), _ptr(gf), _stream(points.device)),
-            "rf_grid_query_backward",
-        )
-        return gd, gf, None, None
+        gd = gf = gp = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gd = torch.zeros_like(first)
+            gf = None if second is None else torch.zeros_like(second)
+            _lib.check(
+                lib.rf_grid_query_backward(C.byref(rf_grid), points.data_ptr(), points.shape[0], g_out.data_ptr(), gd.data_ptr(), _ptr(gf), _stream(points.device)),
+                "rf_grid_query_backward",
+            )
+        if ctx.needs_input_grad[2]:
+            gp = _query_backward_points(rf_grid, points, g_out).to(ctx.points_dtype)
+        return gd, gf, gp, None
+
+
+def _query_backward_points(rf_grid, points: Tensor, g_out: Tensor) -> Tensor:
+    """dL/d(points) [M, 3] float32 of rf_grid_query (rf_grid_query_backward_points)."""
+    gp = torch.empty_like(points)
+    _lib.check(_lib.load().rf_grid_query_backward_points(C.byref(rf_grid), points.data_ptr(), points.shape[0], g_out.data_ptr(), gp.data_ptr(),
+                                                         _stream(points.device)), "rf_grid_query_backward_points")
+    return gp
 
 
 class _InterpolateTensors(torch.autograd.Function):
     """Trilinear interpolation (the bit-exact grid_sample recipe of rf_grid_query) of two EXPLICIT reference-layout tensors
     [X,Y,Z,1] / [X,Y,Z,F] at points [M,3] of a grid's box: no density scale, no activation -- the building block of the composed
-    path, where arbitrary callables run in torch before and after it.  Differentiable w.r.t. both tensors."""
+    path, where arbitrary callables run in torch before and after it.  Differentiable w.r.t. both tensors and the points."""
 
     @staticmethod
     def forward(ctx, dens, feat, points, geometry):
         lib = _lib.load()
         dens = dens.detach().to(torch.float32).contiguous()
         feat = feat.detach().to(torch.float32).contiguous()
+        ctx.points_dtype = points.dtype
         points = points.detach().to(torch.float32).contiguous()
         _require_hip(points, "points")
         rf = _lib.RFGrid()
@@ -892,10 +959,14 @@ class _InterpolateTensors(torch.autograd.Function):
     def backward(ctx, g_out):
         dens, feat, points = ctx.saved_tensors
         g_out = g_out.detach().to(torch.float32).contiguous()
-        gd, gf = torch.zeros_like(dens), torch.zeros_like(feat)
-        _lib.check(_lib.load().rf_grid_query_backward(C.byref(ctx.rf), points.data_ptr(), points.shape[0], g_out.data_ptr(), gd.data_ptr(), gf.data_ptr(),
-                                                      _stream(points.device)), "rf_grid_query_backward")
-        return gd, gf, None, None
+        gd = gf = gp = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gd, gf = torch.zeros_like(dens), torch.zeros_like(feat)
+            _lib.check(_lib.load().rf_grid_query_backward(C.byref(ctx.rf), points.data_ptr(), points.shape[0], g_out.data_ptr(), gd.data_ptr(), gf.data_ptr(),
+                                                          _stream(points.device)), "rf_grid_query_backward")
+        if ctx.needs_input_grad[2]:
+            gp = _query_backward_points(ctx.rf, points, g_out).to(ctx.points_dtype)
+        return gd, gf, gp, None
 
 
 def interpolate_tensors(grid, dens: Tensor, feat: Tensor, points: Tensor) -> Tensor:
@@ -917,7 +988,7 @@ def interpolate_tensors(grid, dens: Tensor, feat: Tensor, points: Tensor) -> Ten
 
 def grid_query(grid: VoxelGrid, points: Tensor) -> Tensor:
     """[M, 3] points -> [M, F+1] = (interpolated features in the reference order, activated density); differentiable
-    w.r.t. the grid (reference VoxelGrid.forward, thre3d_reprs/voxels.py:276-331)."""
+    w.r.t. the grid and the points (reference VoxelGrid.forward, thre3d_reprs/voxels.py:276-331)."""
     if points.dim() != 2 or points.shape[-1] != 3:
         raise AssertionError("points must be [M, 3]")
     first, second = grid.kernel_tensors()
@@ -1058,7 +1129,10 @@ def relu_field_render(
     use_occupancy: bool = False,
 ) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """colour [N,3], depth [N,1], accumulated weight [N,1], disparity [N,1] for flat rays [N,3].
-    Differentiable w.r.t. ``grid.densities`` and ``grid.features`` only (like every reference use).
+    Differentiable w.r.t. the grid tensors (``grid.densities`` / ``grid.features``) and w.r.t. ``origins`` and ``directions``
+    (rf_render_backward_rays: through the samples, the SH direction, the interval lengths and, with ``optimized_sampling``, the
+    slab test's per-ray bounds), like the reference's autograd.  ``t_rand`` gets no gradient (the reference draws it with
+    torch.rand) and ``disparity`` is not differentiable.
     ``t_rand``: None (no jitter), a [N, S] tensor of jitter values, or a ``KeyedJitter``."""
     grid = as_kernel_grid(grid)
     if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
@@ -1082,7 +1156,8 @@ def relu_field_render_pair(grid: VoxelGrid, origins: Tensor, directions: Tensor,
     """``relu_field_render(...)`` and ``relu_field_render(..., render_diffuse=True)`` on the same rays -- the two renders of a training
     iteration (modules/trainers.py:306, 323-325) -- returned as two (colour, depth, acc, disparity) tuples.  Where a gradient is asked
     for and the single op would take the binned adjoint, the pair is ONE autograd node (one forward launch, two backward launches);
-    otherwise it is the two single ops, in the reference's order.  ``t_rands``: the two renders' jitter (each None, [N, S] or KeyedJitter)."""
+    otherwise it is the two single ops, in the reference's order (always when the rays need a gradient).  ``t_rands``: the two renders'
+    jitter (each None, [N, S] or KeyedJitter)."""
     grid = as_kernel_grid(grid)
     if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
         raise AssertionError("the render op works with FLAT rays [N, 3] only")
@@ -1094,7 +1169,8 @@ def relu_field_render_pair(grid: VoxelGrid, origins: Tensor, directions: Tensor,
     ta, tb = grid.kernel_tensors()
     need_grad = torch.is_grad_enabled() and (ta.requires_grad or (tb is not None and tb.requires_grad))
     n = origins.shape[0]
-    if (PAIR_RENDERS and need_grad and n > 0 and _autograd_uses_bricks(grid, flags[0], n, int(num_samples)) and _autograd_uses_bricks(grid, flags[1], n, int(num_samples))):
+    need_rays = torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad)
+    if (PAIR_RENDERS and need_grad and not need_rays and n > 0 and _autograd_uses_bricks(grid, flags[0], n, int(num_samples)) and _autograd_uses_bricks(grid, flags[1], n, int(num_samples))):
         o = _ReluFieldRenderPair.apply(ta, tb, origins, directions, t_rands[0], t_rands[1], grid, int(num_samples), float(near), float(far), flags[0], flags[1])
         return o[:4], o[4:]
     return tuple(_ReluFieldRender.apply(ta, tb, origins, directions, t_rands[i], grid, int(num_samples), float(near), float(far), flags[i], need_grad) for i in range(2))
@@ -1109,12 +1185,37 @@ def _pose_to_host(rotation, translation):
     return (C.c_float * 9)(*rot), (C.c_float * 3)(*trans)
 
 
-def cast_rays_hip(height: int, width: int, focal: float, rotation, translation, device) -> Tuple[Tensor, Tensor]:
-    """All pixel-centre rays of one camera -> (origins, directions) [H, W, 3] float32 on ``device``
-    (reference rendering/volumetric/utils/misc.py:12-50)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"cast_rays runs on a HIP device only (got {device})")
+class _CastRays(torch.autograd.Function):
+    """cast_rays_hip with a learnable pose: the forward is the same kernel (bit-identical rays), the backward
+    dL/dR = sum_pixels g_d (x) c (c = the pixel's camera-space direction) and dL/dt = sum_pixels g_o."""
+
+    @staticmethod
+    def forward(ctx, rotation, translation, height, width, focal, device):
+        ctx.shapes = (rotation.shape, rotation.dtype, rotation.device, translation.shape, translation.dtype, translation.device)
+        ctx.hwf = (int(height), int(width), float(np.float32(focal)))
+        return _cast_rays_launch(height, width, focal, rotation, translation, device)
+
+    @staticmethod
+    def backward(ctx, g_o, g_d):
+        rs, rdt, rdev, ts, tdt, tdev = ctx.shapes
+        H, W, f = ctx.hwf
+        g_r = g_t = None
+        if ctx.needs_input_grad[0]:
+            if g_d is None:
+                g_r = torch.zeros(rs, dtype=rdt, device=rdev)
+            else:
+                dev = g_d.device
+                # camera-space direction of pixel (i, j) in the kernel's float32 order: ((j + .5) - W/2) / f, -((i + .5) - H/2) / f, -1
+                cx = ((torch.arange(W, dtype=torch.float32, device=dev) + 0.5) - np.float32(W * 0.5)) / np.float32(f)
+                cy = -(((torch.arange(H, dtype=torch.float32, device=dev) + 0.5) - np.float32(H * 0.5)) / np.float32(f))
+                cam = torch.stack([cx[None, :].expand(H, W), cy[:, None].expand(H, W), torch.full((H, W), -1.0, device=dev)], dim=-1)
+                g_r = torch.einsum("hwa,hwb->ab", g_d.to(torch.float32), cam).to(rdev, rdt).reshape(rs)
+        if ctx.needs_input_grad[1]:
+            g_t = torch.zeros(ts, dtype=tdt, device=tdev) if g_o is None else g_o.to(torch.float32).reshape(-1, 3).sum(0).to(tdev, tdt).reshape(ts)
+        return g_r, g_t, None, None, None, None
+
+
+def _cast_rays_launch(height, width, focal, rotation, translation, device) -> Tuple[Tensor, Tensor]:
     lib = _lib.load()
     rot, trans = _pose_to_host(rotation, translation)
     o = torch.empty((height, width, 3), dtype=torch.float32, device=device)
@@ -1124,6 +1225,21 @@ def cast_rays_hip(height: int, width: int, focal: float, rotation, translation, 
         "rf_cast_rays",
     )
     return o, d
+
+
+def cast_rays_hip(height: int, width: int, focal: float, rotation, translation, device) -> Tuple[Tensor, Tensor]:
+    """All pixel-centre rays of one camera -> (origins, directions) [H, W, 3] float32 on ``device``
+    (reference rendering/volumetric/utils/misc.py:12-50).  Differentiable w.r.t. ``rotation`` / ``translation`` when they are
+    tensors that require a gradient (camera pose refinement); the rays are the same kernel's either way."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"cast_rays runs on a HIP device only (got {device})")
+    learn = torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in (rotation, translation))
+    if learn:
+        rot = rotation if isinstance(rotation, Tensor) else torch.as_tensor(rotation, dtype=torch.float32)
+        trans = translation if isinstance(translation, Tensor) else torch.as_tensor(translation, dtype=torch.float32)
+        return _CastRays.apply(rot, trans, int(height), int(width), float(focal), device)
+    return _cast_rays_launch(height, width, focal, rotation, translation, device)
 
 
 def cast_selected_rays_hip(height: int, width: int, focal: float, poses: Tensor, pixel_index: Tensor) -> Tuple[Tensor, Tensor]:

@@ -204,7 +204,8 @@ def render_sh_voxel_grid_frame(
     """The pixels [first_ray, first_ray + num_rays) of a whole posed-camera frame (row-major; default all of it) in ONE kernel
     launch: what ``VolumetricModel.render`` does per chunk -- cast_rays, slice, ``torch.rand``, render, concatenate
     (reference modules/volumetric_model.py:143-172) -- with the rays and the stratified jitter generated inside the kernel.
-    Inference only (no autograd); results do not depend on how a frame is split into calls.  Configurations that ask for torch's own
+    Inference only (no autograd, in particular none w.r.t. the camera pose: use ``cast_rays`` + ``render_sh_voxel_grid`` for that);
+    results do not depend on how a frame is split into calls.  Configurations that ask for torch's own
     random streams -- ``consume_reference_rng``, or ``perturb_sampled_points`` with ``jitter="torch"`` (a torch.rand table per chunk) --
     are served the way ``VolumetricModel.render`` serves them: cast_rays, then ``render_sh_voxel_grid`` on chunks of
     ``parallel_rays_chunk_size`` rays of the range, concatenated (the reference's loop, volumetric_model.py:152-172)."""

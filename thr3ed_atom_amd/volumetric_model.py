@@ -28,7 +28,8 @@ from .renderers import RenderConfig, RenderProcedure, render_sh_voxel_grid, rend
 
 def cast_rays(camera_intrinsics: CameraIntrinsics, pose: CameraPose, device=None) -> Rays:
     """Rays [H, W, 3] of a posed pinhole camera on a HIP device
-    (reference rendering/volumetric/utils/misc.py:12-50)."""
+    (reference rendering/volumetric/utils/misc.py:12-50).  Differentiable w.r.t. ``pose.rotation`` / ``pose.translation`` when they are
+    tensors that require a gradient (camera pose refinement, ``refine_camera_pose``)."""
     device = torch.device("cuda" if device is None else device)
     height, width, focal = camera_intrinsics
     o, d = cast_rays_hip(int(height), int(width), float(focal), pose.rotation, pose.translation, device)
@@ -117,7 +118,8 @@ class VolumetricModel:
         data_parallel: bool = False,
         **kwargs,
     ) -> RenderOut:
-        """Full-image render under no_grad: cast rays, render them in chunks of
+        """Full-image render under no_grad (not differentiable w.r.t. the pose, as in the reference; use ``cast_rays`` +
+        ``render_rays`` for that): cast rays, render them in chunks of
         ``parallel_rays_chunk_size`` (None = one chunk), concatenate and reshape to [H, W, .]
         (reference :116-174).  The fused kernel does not need chunking for memory; the argument is
         honoured so that outputs and RNG consumption follow the reference chunk by chunk.
