@@ -223,8 +223,9 @@ int rf_render_backward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flag
  *
  *   key  = ((((bx * 2 + f_x) * NBY + by) * NBZ + bz) << 2) | f_y | f_z << 1;  (bx, by, bz) = the brick (brick_size^3 nodes,
  *          brick_size in {4, 8}; or RF_BRICK_4X8X8: 4 x 8 x 8 nodes, the bricks of the single-GPU optimizer pass -- four
- *          256-thread workgroups per CU instead of two 512-thread ones; accepted by the render / emit / offset functions and
- *          by rf_brick_accumulate_adam and rf_train_step, SH degree 0 or 2, every grid tensor below 2^30 elements)
+ *          256-thread workgroups per CU instead of two 512-thread ones; accepted by the render / emit / offset functions, by
+ *          rf_brick_accumulate, rf_brick_accumulate_adam[_mirror|_range] and rf_train_step: SH degree 0 or 2 -- or base-channel lists
+ *          alone --, and with the optimizer every grid tensor below 2^30 elements)
  *          holding the LOWER node of the sample's cell;  f_a = the cell's upper node on axis a belongs
  *          to the next brick (so the record also touches that neighbour's nodes).  8 * nbricks keys.  The order is x-slab
  *          major with the x flag directly below the slab index: everything that touches the nodes of the x-slabs [s0, s1)
@@ -256,7 +257,17 @@ int rf_render_backward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flag
  * element of the gradient tensors (no zero-fill needed; diffuse lists: only density + degree-0 gradients), accumulate = 1
  * adds.  Up to 16 lists per call, at most 8 of a kind, the full-width lists first: (specular list, render_diffuse list) = BOTH
  * renders of a training iteration (modules/trainers.py:306-341) in one pass (the base-channel records go into the first four
- * channel columns of the same accumulators); under data parallelism one pair per source rank.  Any SH degree (degree 3: brick_size 8). */
+ * channel columns of the same accumulators); under data parallelism one pair per source rank.  Cubic bricks take any SH degree: what
+ * decides is the LDS check of the launch (batch buffers or accumulator image above 150 KB are refused), and degree 3 passes it with
+ * brick_size 8 (123 KB, one workgroup per CU) as well as with brick_size 4.  A call whose lists are all render_diffuse lists runs on
+ * the four base channels whatever the grid's degree and leaves every higher-degree element untouched.
+ * RF_ERR_UNSUPPORTED combinations of the brick pass (checked before anything is launched; tests/test_hip_brick_matrix.py asserts them):
+ *   - RF_BRICK_4X8X8 with full-width lists on a grid of SH degree 1 or 3 (rf_brick_accumulate and the optimizer variants alike);
+ *   - the optimizer variants with accumulate semantics, on RF_LAYOUT_REFERENCE, on a grid of SH degree 1 or 3, or with base-channel
+ *     lists alone on an SH grid (the update needs the complete gradient of whole float4s);
+ *   - RF_BRICK_4X8X8 with the optimizer when a grid tensor has 2^30 elements or more, or the padded grid more than 2^24 nodes;
+ *   - rf_brick_accumulate_adam_mirror unless RF_BRICK_4X8X8, RF_LAYOUT_SPLIT, the whole grid, dims multiples of (4, 8, 8);
+ *   - rf_brick_accumulate_adam_split unless brick_size 8 and the one-round flush. */
 typedef struct RFBrickList {
   const float* records_sorted_dev; /* [capacity, rf_expanded_record_floats(F)] (diffuse lists: F = 3) */
   const int64_t* offsets_dev;      /* [8 * nbricks + 1] start of each (brick, flags) class            */

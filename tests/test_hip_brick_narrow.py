@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import thr3ed_atom_amd as rf
+from tests import brick_lists as bl
 from thr3ed_atom_amd import ops
 
 pytestmark = pytest.mark.gpu
@@ -14,95 +15,27 @@ pytestmark = pytest.mark.gpu
 K = 9
 C = 3 * K + 1
 EDGES = (4, 8, 8)
-SH_C0 = 0.28209479177387814
-SH_C1 = 0.4886025119029199
-SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396)
-
-
-def sh_basis(v):
-    x, y, z = v[:, 0], v[:, 1], v[:, 2]
-    xx, yy, zz = x * x, y * y, z * z
-    return np.stack([np.full_like(x, SH_C0), -SH_C1 * y, SH_C1 * z, -SH_C1 * x, SH_C2[0] * x * y, SH_C2[1] * y * z,
-                     SH_C2[2] * (2 * zz - xx - yy), SH_C2[3] * x * z, SH_C2[4] * (xx - yy)], axis=1)
-
-
-def channel_values(rec, wide):
-    """[n, C] per-node channel values of records (0 = density, 1..3 = degree 0 of r, g, b, 4 + 8 colour + k - 1 = degree k)"""
-    out = np.zeros((len(rec), C))
-    out[:, 0] = rec[:, 3] if wide else rec[:, 4]
-    if not wide:
-        out[:, 1:4] = rec[:, 5:8]
-        return out
-    Y = sh_basis(rec[:, 7:10])
-    graw = rec[:, 4:7]
-    out[:, 1:4] = graw * SH_C0
-    for colour in range(3):
-        out[:, 4 + 8 * colour: 12 + 8 * colour] = graw[:, colour: colour + 1] * Y[:, 1:]
-    return out
 
 
 def brick_key(lower, dims, nb):
-    b = [lower[:, a] // EDGES[a] for a in range(3)]
-    f = [((lower[:, a] + 1 < dims[a]) & ((lower[:, a] + 1) // EDGES[a] != b[a])).astype(np.int64) for a in range(3)]
-    return ((((b[0] * 2 + f[0]) * nb[1] + b[1]) * nb[2] + b[2]) << 2) | f[1] | (f[2] << 1)
+    assert tuple(nb) == bl.brick_counts(dims, EDGES)
+    return bl.brick_key(lower, dims, EDGES)
 
 
 def sorted_list(rec, dims, nb, device):
     """records [n, 8 or 12] -> (records in key order, int64 offsets of the 8 * num_bricks key classes)"""
-    nkeys = nb[0] * nb[1] * nb[2] * 8
-    keys = brick_key(np.floor(rec[:, :3]).astype(np.int64), dims, nb)
-    order = np.argsort(keys, kind="stable")
-    offsets = np.searchsorted(keys[order], np.arange(nkeys + 1)).astype(np.int64)
-    offsets[-1] = len(rec)
-    return torch.from_numpy(rec[order].astype(np.float32)).to(device), torch.from_numpy(offsets).to(device)
+    assert tuple(nb) == bl.brick_counts(dims, EDGES)
+    (records, offsets), = bl.sorted_lists(rec, dims, EDGES, num_lists=1, base=0, tail=0)
+    return torch.from_numpy(records).to(device), torch.from_numpy(offsets).to(device)
 
 
 def scatter(rec, wide, dims):
     """float64 trilinear scatter-add of the records' channel values onto the nodes of the grid: [X, Y, Z, C]"""
-    out = np.zeros(tuple(dims) + (C,))
-    pos = rec[:, :3].astype(np.float32)
-    fl = np.floor(pos)
-    lo = fl.astype(np.int64)
-    whi = (pos - fl).astype(np.float64)
-    wlo = ((fl + 1) - pos).astype(np.float64)
-    vals = channel_values(rec.astype(np.float32).astype(np.float64), wide)
-    for d in range(8):
-        dd = ((d >> 2) & 1, (d >> 1) & 1, d & 1)
-        node = lo + np.array(dd)
-        w = np.prod([whi[:, a] if dd[a] else wlo[:, a] for a in range(3)], axis=0)
-        inside = np.all((node >= 0) & (node < np.array(dims)), axis=1)
-        np.add.at(out, (node[inside, 0], node[inside, 1], node[inside, 2]), w[inside, None] * vals[inside])
-    return out
+    return bl.scatter(rec, wide, dims, K)[0]
 
 
 def crafted_records(dims, seed):
-    """(full-width records [n, 12], base-channel records [m, 8]).  Base-channel records: one per lower node of the lattice of every
-    node (every brick face, edge and corner), more at random, 300 in one cell (several batches for one brick); full-width records
-    only at lower x <= 6 and base-channel ones only at lower x >= 4 (bricks with one kind only); nothing that reaches a node with
-    y >= 8 and z >= 16 (empty bricks)."""
-    rng = np.random.default_rng(seed)
-    X, Y, Z = dims
-
-    def positions(lower):
-        return lower + rng.uniform(0.0, 1.0, size=lower.shape).astype(np.float32)
-
-    lat = np.stack(np.meshgrid(np.arange(X), np.arange(Y), np.arange(Z), indexing="ij"), -1).reshape(-1, 3)
-    narrow_lower = np.concatenate([lat[lat[:, 0] >= 4], np.tile([[6, 3, 5]], (300, 1)),
-                                   rng.integers(0, np.array(dims), size=(2000, 3))])
-    narrow_lower = narrow_lower[narrow_lower[:, 0] >= 4]
-    wide_lower = np.concatenate([lat[(lat[:, 0] <= 6) & (lat % 3 == 0).any(axis=1)], rng.integers(0, np.array(dims), size=(1500, 3))])
-    wide_lower = wide_lower[wide_lower[:, 0] <= 6]
-    keep = lambda lo: ~((lo[:, 1] + 1 >= 8) & (lo[:, 2] + 1 >= 16))
-    narrow_lower, wide_lower = narrow_lower[keep(narrow_lower)], wide_lower[keep(wide_lower)]
-    narrow = np.zeros((len(narrow_lower), 8), np.float32)
-    narrow[:, :3] = positions(narrow_lower)
-    narrow[:, 4:8] = rng.uniform(-1.0, 1.0, size=(len(narrow), 4))
-    wide = np.zeros((len(wide_lower), 12), np.float32)
-    wide[:, :3] = positions(wide_lower)
-    wide[:, 3:7] = rng.uniform(-1.0, 1.0, size=(len(wide), 4))
-    v = rng.normal(size=(len(wide), 3))
-    wide[:, 7:10] = v / np.linalg.norm(v, axis=1, keepdims=True)
-    return wide, narrow
+    return bl.narrow_pass_records(dims, seed)
 
 
 def make_grid(dims, device, seed=3):
@@ -115,11 +48,7 @@ def make_grid(dims, device, seed=3):
 
 def to_reference(g):
     """[..., C] in channel order -> (densities [..., 1], features [..., 27], index = colour * 9 + k)"""
-    feat = np.zeros(g.shape[:-1] + (3 * K,))
-    for colour in range(3):
-        feat[..., colour * K] = g[..., 1 + colour]
-        feat[..., colour * K + 1: colour * K + K] = g[..., 4 + 8 * colour: 12 + 8 * colour]
-    return g[..., :1], feat
+    return bl.to_reference(g, K)
 
 
 def lists_for(kinds, wide, narrow, dims, nb, device):
