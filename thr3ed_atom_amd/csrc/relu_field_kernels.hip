@@ -4354,9 +4354,27 @@ __global__ __launch_bounds__(1024) void loss_and_offsets_kernel(L1Sets sets, con
 // ---------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ---------------------------------------------------------------------------------------------
+// split / bricked storage at SH degree 0 keeps all four channels in the first tensor: the second tensor -- parameters or
+// gradients -- may then be null
+bool second_tensor_optional(const RFGrid* g) { return g->layout != RF_LAYOUT_REFERENCE && g->num_features == 3; }
+
+// the node count, every axis padded to whole 8-node bricks where `whole_bricks` says so
+unsigned long long node_count(const RFGrid* g, bool whole_bricks) {
+  unsigned long long nodes = 1;
+  for (int a = 0; a < 3; ++a) nodes *= (unsigned long long)(whole_bricks ? (g->dims[a] + 7) / 8 * 8 : g->dims[a]);
+  return nodes;
+}
+
+// an A/B switch of the environment as an integer (`fallback` when unset); the callers that read one once per process keep it in a static
+int env_int(const char* name, int fallback) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : fallback;
+}
+bool env_flag(const char* name, bool fallback) { return env_int(name, fallback) != 0; }
+
 int check_grid(const RFGrid* g) {
   if (!g || !g->densities_dev) return RF_ERR_NULL_POINTER;
-  if (!g->features_dev && !(g->layout != RF_LAYOUT_REFERENCE && g->num_features == 3)) return RF_ERR_NULL_POINTER;
+  if (!g->features_dev && !second_tensor_optional(g)) return RF_ERR_NULL_POINTER;
   for (int a = 0; a < 3; ++a)
     if (g->dims[a] < 1 || g->dims[a] > 2046) return RF_ERR_BAD_SHAPE;
   const int F = g->num_features;
@@ -4371,11 +4389,7 @@ int check_grid(const RFGrid* g) {
   }
   // node indices are 32-bit in the kernels (node_lin: 24-bit multiplies into an unsigned int; element offsets are 64-bit):
   // the node count, padded to whole bricks for the bricked order, must stay below 2^32
-  {
-    unsigned long long nodes = 1;
-    for (int a = 0; a < 3; ++a) nodes *= (unsigned long long)(g->layout == RF_LAYOUT_BRICKED ? (g->dims[a] + 7) / 8 * 8 : g->dims[a]);
-    if (nodes >= (1ull << 32)) return RF_ERR_BAD_SHAPE;
-  }
+  if (node_count(g, g->layout == RF_LAYOUT_BRICKED) >= (1ull << 32)) return RF_ERR_BAD_SHAPE;
   return RF_OK;
 }
 
@@ -4415,8 +4429,7 @@ GridArgs to_args(const RFGrid* g) {
     a.step[2] = a.jump[2] = 1u;
   }
   {
-    unsigned long long nodes = 1;
-    for (int i = 0; i < 3; ++i) nodes *= (unsigned long long)(a.bricked ? (g->dims[i] + 7) / 8 * 8 : g->dims[i]);
+    const unsigned long long nodes = node_count(g, a.bricked);
     const unsigned long long db = (unsigned long long)a.dstride * 4ull, fb = (unsigned long long)a.fstride * 4ull;
     const uintptr_t d0 = reinterpret_cast<uintptr_t>(a.dens), f0 = a.feat ? reinterpret_cast<uintptr_t>(a.feat) : d0;
     const uintptr_t lo = d0 < f0 ? d0 : f0;
@@ -4427,7 +4440,7 @@ GridArgs to_args(const RFGrid* g) {
     a.feat_off = (unsigned int)(f0 - lo);
     a.near32 = nodes <= (1ull << 24) && db < (1ull << 24) && fb < (1ull << 24) && span < (1ull << 32);
     // ($RF_FAR_ADDRESSING=1: the general 64-bit path on grids that would not need it -- tests compare the two)
-    if (const char* e = getenv("RF_FAR_ADDRESSING")) a.near32 = a.near32 && atoi(e) == 0;
+    a.near32 = a.near32 && env_int("RF_FAR_ADDRESSING", 0) == 0;
   }
   return a;
 }
@@ -4489,24 +4502,25 @@ OutArgs to_args(const RFRenderOut* o) {
 
 int launch_status() { return hipGetLastError() == hipSuccess ? RF_OK : RF_ERR_LAUNCH; }
 
-template <int K, bool DIFFUSE>
-void launch_forward(bool save, unsigned blocks, hipStream_t st, const GridArgs& g, const RayArgs& r, const OutArgs& o,
-                    uint32_t flags) {
-  if (save)
-    hipLaunchKernelGGL((render_forward_kernel<K, DIFFUSE, true>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, flags);
-  else
-    hipLaunchKernelGGL((render_forward_kernel<K, DIFFUSE, false>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, flags);
+// The one place that turns the SH degree into a kernel instantiation: f(std::integral_constant<int, K>) for the K = (degree + 1)^2
+// coefficients per colour of the grid, if K is in the set the caller allows -- the set is what gets instantiated; RF_ERR_UNSUPPORTED
+// otherwise.  f returns the call's return code.
+template <int... Ks>
+struct ShSet {};
+using ShAll = ShSet<1, 4, 9, 16>;
+using ShEven = ShSet<1, 9>;  // SH degree 0 / 2: 3 K + 1 channels are whole float4s
+template <int... Ks, class F>
+int dispatch_sh(int K, ShSet<Ks...>, F&& f) {
+  int rc = RF_ERR_UNSUPPORTED;
+  (void)(... || (K == Ks && ((rc = f(std::integral_constant<int, Ks>{})), true)));
+  return rc;
 }
 
-template <int K, bool DIFFUSE>
-void launch_backward(unsigned blocks, hipStream_t st, const GridArgs& g, const RayArgs& r, const OutArgs& o,
-                     const GradArgs& gr, uint32_t flags) {
-  if (gr.sorted)
-    hipLaunchKernelGGL((render_emit_direct_kernel<K, DIFFUSE>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags);
-  else if (gr.keys)
-    hipLaunchKernelGGL((render_backward_kernel<K, DIFFUSE, 1>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags);
-  else
-    hipLaunchKernelGGL((render_backward_kernel<K, DIFFUSE, 0>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags);
+// the render kernels <K, DIFFUSE>: a render_diffuse pass reads one coefficient per colour, like SH degree 0
+template <class F>
+int dispatch_render(int K, bool diffuse, F&& f) {
+  if (diffuse || K == 1) return f(std::integral_constant<int, 1>{}, std::true_type{});
+  return dispatch_sh(K, ShSet<4, 9, 16>{}, [&](auto k) { return f(k, std::false_type{}); });
 }
 
 unsigned grid_1d(long long n, int block, long long cap = 256LL * 16) {
@@ -4653,7 +4667,48 @@ static int brick_geometry(const RFGrid* grid, int brick_size, int* shift, int nb
   return (total * 8 - 1 <= (short_keys ? 0x7fffLL : (1LL << 21) - 1)) ? RF_OK : RF_ERR_UNSUPPORTED;
 }
 
+// the sample cache of a saving forward render: all four arrays or none
+static bool has_caches(const RFRenderOut* o) { return o->sample_cache_dev && o->trans_cache_dev && o->stop_cache_dev && o->chunk_mask_dev; }
 
+// RFRenderOut.key_hist_dev: the forward render counts the records of the binned backward per (brick, flags) key
+static int set_key_hist(const RFGrid* grid, const RFRenderOut* out, OutArgs* o) {
+  int shift, nb[3];
+  const int rc = brick_geometry(grid, out->brick_size, &shift, nb, false);
+  if (rc != RF_OK) return rc;
+  o->hist = out->key_hist_dev;
+  o->brick_shift = shift;
+  o->nby = nb[1];
+  o->nbz = nb[2];
+  return RF_OK;
+}
+
+// the adjoint that writes its records straight into the sorted list (render_emit_direct_kernel): cursors, list, key geometry
+static int emit_direct_args(const RFGrid* grid, int32_t brick_size, int32_t* cursor_dev, float* records_sorted_dev, int32_t* hist_clear_dev, GradArgs* gr) {
+  if (!cursor_dev || !records_sorted_dev) return RF_ERR_NULL_POINTER;
+  int shift, nb[3];
+  const int rc = brick_geometry(grid, brick_size, &shift, nb, false);
+  if (rc != RF_OK) return rc;
+  *gr = GradArgs{};
+  gr->cursor = cursor_dev;
+  gr->sorted = reinterpret_cast<float4*>(records_sorted_dev);
+  gr->hist_clear = hist_clear_dev;
+  gr->nkeys = nb[0] * nb[1] * nb[2] * 8;
+  gr->brick_shift = shift;
+  gr->nby = nb[1];
+  gr->nbz = nb[2];
+  return RF_OK;
+}
+
+static void set_grads(const RFRenderGrads* grads, GradArgs* gr) {
+  gr->gcolour = grads->grad_colour_dev;
+  gr->gdepth = grads->grad_depth_dev;
+  gr->gacc = grads->grad_acc_dev;
+}
+
+// the two renders of a training iteration go into one launch when they cover the same rays, [0] specular and [1] render_diffuse
+static bool renders_pair_up(const RFRayBatch* const rays[2], const uint32_t flags[2]) {
+  return rays[0]->num_rays == rays[1]->num_rays && !(flags[0] & RF_FLAG_RENDER_DIFFUSE) && (flags[1] & RF_FLAG_RENDER_DIFFUSE);
+}
 
 // Which kernel renders a frame of a posed camera (RFRayBatch.camera, no sample cache): ray packets -- one wave per 8 x 8 pixel tile,
 // render_frame_tile_kernel -- where a tile's rays stay within ~2 voxels of each other at the volume's centre (8 pixels x distance /
@@ -4697,21 +4752,16 @@ int rf_render_forward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags
   if (rays->num_rays == 0) return RF_OK;
   if (!out->colour_dev || !out->depth_dev || !out->acc_dev || !out->disparity_dev) return RF_ERR_NULL_POINTER;
   const bool save = out->sample_cache_dev != nullptr;
-  if (save && (!out->trans_cache_dev || !out->stop_cache_dev || !out->chunk_mask_dev)) return RF_ERR_NULL_POINTER;
+  if (save && !has_caches(out)) return RF_ERR_NULL_POINTER;
   if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
 
   const GridArgs g = to_args(grid);
   const RayArgs r = to_args(rays, flags);
   OutArgs o = to_args(out);
-  if (out->key_hist_dev) {  // count the records of the binned backward per (brick, flags) key
+  if (out->key_hist_dev) {
     if (!save) return RF_ERR_NULL_POINTER;
-    int shift, nb[3];
-    rc = brick_geometry(grid, out->brick_size, &shift, nb, false);
+    rc = set_key_hist(grid, out, &o);
     if (rc != RF_OK) return rc;
-    o.hist = out->key_hist_dev;
-    o.brick_shift = shift;
-    o.nby = nb[1];
-    o.nbz = nb[2];
   }
   const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
   hipStream_t st = (hipStream_t)stream;
@@ -4728,45 +4778,32 @@ int rf_render_forward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags
       const int row0 = (int)(rays->first_ray / W), row1 = (int)((rays->first_ray + rays->num_rays - 1) / W);
       const int tile_rows = (row1 - row0) / 8 + 1, tiles_x = (W + 7) / 8;
       // (scheduling of the tiles: $RF_TILE_WPB = waves per workgroup, 1 or 4; $RF_TILE_XCD_ROWS = 0 / 1: A/B switches, read once)
-      static const int wpb = [] {
-        const char* e = getenv("RF_TILE_WPB");
-        return (e && atoi(e) == 4) ? 4 : 1;
-      }();
-      static const bool xcd_rows = [] {
-        const char* e = getenv("RF_TILE_XCD_ROWS");
-        return e ? atoi(e) != 0 : true;
-      }();
+      static const int wpb = env_int("RF_TILE_WPB", 1) == 4 ? 4 : 1;
+      static const bool xcd_rows = env_flag("RF_TILE_XCD_ROWS", true);
       const int KT = diffuse ? 1 : K;  // coefficients per colour that are read
-      const bool sched_default = KT == 4 || KT == 16;  // (the degree-1 / 3 instantiations exist in the default scheduling only)
-      const int wpb_ = sched_default ? 1 : wpb;
-      const bool xr_ = sched_default ? true : xcd_rows;
-      const long long wgs = xr_ ? (long long)((tile_rows + 7) / 8) * 8 * ((tiles_x + wpb_ - 1) / wpb_) : ((long long)tile_rows * tiles_x + wpb_ - 1) / wpb_;
-#define RF_TILE_LAUNCH(K_, WPB_, XR_)                                                                                                            \
-  hipLaunchKernelGGL((render_frame_tile_kernel<K_, WPB_, XR_>), dim3((unsigned)wgs), dim3(kWave * WPB_), 0, st, g, r, o, flags, row0, tile_rows, tiles_x)
-      if (KT == 4) {
-        RF_TILE_LAUNCH(4, 1, true);
-      } else if (KT == 16) {
-        RF_TILE_LAUNCH(16, 1, true);
-      } else if (KT == 9) {
-        if (wpb == 4) { if (xcd_rows) RF_TILE_LAUNCH(9, 4, true); else RF_TILE_LAUNCH(9, 4, false); }
-        else { if (xcd_rows) RF_TILE_LAUNCH(9, 1, true); else RF_TILE_LAUNCH(9, 1, false); }
-      } else {
-        if (wpb == 4) { if (xcd_rows) RF_TILE_LAUNCH(1, 4, true); else RF_TILE_LAUNCH(1, 4, false); }
-        else { if (xcd_rows) RF_TILE_LAUNCH(1, 1, true); else RF_TILE_LAUNCH(1, 1, false); }
-      }
-#undef RF_TILE_LAUNCH
-      return launch_status();
+      auto launch = [&](auto k, auto waves, auto xr) {  // render_frame_tile_kernel<K, WPB, XCD_ROWS>
+        constexpr int WPB = decltype(waves)::value;
+        const long long wgs = decltype(xr)::value ? (long long)((tile_rows + 7) / 8) * 8 * ((tiles_x + WPB - 1) / WPB) : ((long long)tile_rows * tiles_x + WPB - 1) / WPB;
+        hipLaunchKernelGGL((render_frame_tile_kernel<decltype(k)::value, WPB, decltype(xr)::value>), dim3((unsigned)wgs), dim3(kWave * WPB), 0, st, g, r, o, flags, row0, tile_rows, tiles_x);
+        return launch_status();
+      };
+      using One = std::integral_constant<int, 1>;
+      using Four = std::integral_constant<int, 4>;
+      if (KT == 4 || KT == 16)  // (the degree-1 / 3 instantiations exist in the default scheduling only)
+        return dispatch_sh(KT, ShSet<4, 16>{}, [&](auto k) { return launch(k, One{}, std::true_type{}); });
+      return dispatch_sh(KT, ShSet<9, 1>{}, [&](auto k) {  // (in the order the kernels have always been emitted: the code object keeps its layout)
+        if (wpb == 4) return xcd_rows ? launch(k, Four{}, std::true_type{}) : launch(k, Four{}, std::false_type{});
+        return xcd_rows ? launch(k, One{}, std::true_type{}) : launch(k, One{}, std::false_type{});
+      });
     }
   }
-  if (diffuse || K == 1)
-    launch_forward<1, true>(save, blocks, st, g, r, o, flags);
-  else if (K == 4)
-    launch_forward<4, false>(save, blocks, st, g, r, o, flags);
-  else if (K == 9)
-    launch_forward<9, false>(save, blocks, st, g, r, o, flags);
-  else
-    launch_forward<16, false>(save, blocks, st, g, r, o, flags);
-  return launch_status();
+  return dispatch_render(K, diffuse, [&](auto k, auto d) {
+    if (save)
+      hipLaunchKernelGGL((render_forward_kernel<decltype(k)::value, decltype(d)::value, true>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, flags);
+    else
+      hipLaunchKernelGGL((render_forward_kernel<decltype(k)::value, decltype(d)::value, false>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, flags);
+    return launch_status();
+  });
 }
 
 // both saving forward renders of a training iteration (0 = specular, 1 = render_diffuse) over the same rays in ONE launch
@@ -4780,33 +4817,24 @@ static int forward_pair_impl(const RFGrid* grid, const RFRayBatch* const rays[2]
     if (rc != RF_OK) return rc;
     const RFRenderOut* out = outs[i];
     if (!out || !out->colour_dev || !out->depth_dev || !out->acc_dev || !out->disparity_dev) return RF_ERR_NULL_POINTER;
-    if (!out->sample_cache_dev || !out->trans_cache_dev || !out->stop_cache_dev || !out->chunk_mask_dev) return RF_ERR_UNSUPPORTED;
+    if (!has_caches(out)) return RF_ERR_UNSUPPORTED;  // (not a saving render: nothing to pair, the caller falls back to single launches)
     if ((flags[i] & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
     p.r[i] = to_args(rays[i], flags[i]);
     p.out[i] = to_args(out);
     p.flags[i] = flags[i];
     if (out->key_hist_dev) {
-      int shift, nb[3];
-      rc = brick_geometry(grid, out->brick_size, &shift, nb, false);
+      rc = set_key_hist(grid, out, &p.out[i]);
       if (rc != RF_OK) return rc;
-      p.out[i].hist = out->key_hist_dev;
-      p.out[i].brick_shift = shift;
-      p.out[i].nby = nb[1];
-      p.out[i].nbz = nb[2];
     }
   }
-  if (rays[0]->num_rays != rays[1]->num_rays || (flags[0] & RF_FLAG_RENDER_DIFFUSE) || !(flags[1] & RF_FLAG_RENDER_DIFFUSE)) return RF_ERR_UNSUPPORTED;
+  if (!renders_pair_up(rays, flags)) return RF_ERR_UNSUPPORTED;
   if (rays[0]->num_rays == 0) return RF_OK;
   const GridArgs g = to_args(grid);
   const unsigned blocks = (unsigned)((rays[0]->num_rays + 1) / 2);
-  hipStream_t st = (hipStream_t)stream;
-  switch (grid->num_features / 3) {
-    case 1: hipLaunchKernelGGL((render_forward_pair_kernel<1>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-    case 4: hipLaunchKernelGGL((render_forward_pair_kernel<4>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-    case 9: hipLaunchKernelGGL((render_forward_pair_kernel<9>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-    default: hipLaunchKernelGGL((render_forward_pair_kernel<16>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-  }
-  return launch_status();
+  return dispatch_sh(grid->num_features / 3, ShAll{}, [&](auto k) {
+    hipLaunchKernelGGL((render_forward_pair_kernel<decltype(k)::value>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
+    return launch_status();
+  });
 }
 
 static int backward_impl(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, const RFRenderOut* fwd,
@@ -4817,32 +4845,30 @@ static int backward_impl(const RFGrid* grid, const RFRayBatch* rays, uint32_t fl
   if (rc != RF_OK) return rc;
   if (!fwd || !grads) return RF_ERR_NULL_POINTER;
   if (rays->num_rays == 0) return RF_OK;
-  if (!fwd->sample_cache_dev || !fwd->trans_cache_dev || !fwd->stop_cache_dev || !fwd->chunk_mask_dev) return RF_ERR_NULL_POINTER;
+  if (!has_caches(fwd)) return RF_ERR_NULL_POINTER;
   const GridArgs g = to_args(grid);
   const RayArgs r = to_args(rays, flags);
   const OutArgs o = to_args(fwd);
-  gr.gcolour = grads->grad_colour_dev;
-  gr.gdepth = grads->grad_depth_dev;
-  gr.gacc = grads->grad_acc_dev;
+  set_grads(grads, &gr);
   const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
   hipStream_t st = (hipStream_t)stream;
-  const bool diffuse = flags & RF_FLAG_RENDER_DIFFUSE;
-  const int K = grid->num_features / 3;
-  if (diffuse || K == 1)
-    launch_backward<1, true>(blocks, st, g, r, o, gr, flags);
-  else if (K == 4)
-    launch_backward<4, false>(blocks, st, g, r, o, gr, flags);
-  else if (K == 9)
-    launch_backward<9, false>(blocks, st, g, r, o, gr, flags);
-  else
-    launch_backward<16, false>(blocks, st, g, r, o, gr, flags);
-  return launch_status();
+  return dispatch_render(grid->num_features / 3, flags & RF_FLAG_RENDER_DIFFUSE, [&](auto k, auto d) {
+    constexpr int K = decltype(k)::value;
+    constexpr bool DIFFUSE = decltype(d)::value;
+    if (gr.sorted)
+      hipLaunchKernelGGL((render_emit_direct_kernel<K, DIFFUSE>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags);
+    else if (gr.keys)
+      hipLaunchKernelGGL((render_backward_kernel<K, DIFFUSE, 1>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags);
+    else
+      hipLaunchKernelGGL((render_backward_kernel<K, DIFFUSE, 0>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags);
+    return launch_status();
+  });
 }
 
 int rf_render_backward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, const RFRenderOut* fwd,
                        const RFRenderGrads* grads, float* grad_densities_dev, float* grad_features_dev, void* stream) {
   if (!grad_densities_dev) return RF_ERR_NULL_POINTER;
-  if (grid && !grad_features_dev && !(grid->layout != RF_LAYOUT_REFERENCE && grid->num_features == 3)) return RF_ERR_NULL_POINTER;
+  if (grid && !grad_features_dev && !second_tensor_optional(grid)) return RF_ERR_NULL_POINTER;
   GradArgs gr = {};
   gr.gdens = grad_densities_dev;
   gr.gfeat = grad_features_dev;
@@ -4879,36 +4905,22 @@ static int emit_pair_impl(const RFGrid* grid, const RFRayBatch* const rays[2], c
     const RFPassScratch& ps = *pass[i];
     const RFRenderOut* fwd = &ps.out;
     if (!ps.cursor_dev || !ps.records_sorted_dev || !ps.grad_colour_dev) return RF_ERR_NULL_POINTER;
-    if (!fwd->sample_cache_dev || !fwd->trans_cache_dev || !fwd->stop_cache_dev || !fwd->chunk_mask_dev) return RF_ERR_NULL_POINTER;
-    int shift, nb[3];
-    rc = brick_geometry(grid, fwd->brick_size, &shift, nb, false);
+    if (!has_caches(fwd)) return RF_ERR_NULL_POINTER;
+    rc = emit_direct_args(grid, fwd->brick_size, ps.cursor_dev, ps.records_sorted_dev, fwd->key_hist_dev, &p.gr[i]);
     if (rc != RF_OK) return rc;
+    p.gr[i].gcolour = ps.grad_colour_dev;
     p.r[i] = to_args(rays[i], flags[i]);
     p.fwd[i] = to_args(fwd);
     p.flags[i] = flags[i];
-    GradArgs gr = {};
-    gr.cursor = ps.cursor_dev;
-    gr.sorted = reinterpret_cast<float4*>(ps.records_sorted_dev);
-    gr.hist_clear = fwd->key_hist_dev;
-    gr.nkeys = nb[0] * nb[1] * nb[2] * 8;
-    gr.brick_shift = shift;
-    gr.nby = nb[1];
-    gr.nbz = nb[2];
-    gr.gcolour = ps.grad_colour_dev;
-    p.gr[i] = gr;
   }
-  if (rays[0]->num_rays != rays[1]->num_rays || (flags[0] & RF_FLAG_RENDER_DIFFUSE) || !(flags[1] & RF_FLAG_RENDER_DIFFUSE)) return RF_ERR_UNSUPPORTED;
+  if (!renders_pair_up(rays, flags)) return RF_ERR_UNSUPPORTED;
   if (rays[0]->num_rays == 0) return RF_OK;
   const GridArgs g = to_args(grid);
   const unsigned blocks = (unsigned)((rays[0]->num_rays + 1) / 2);
-  hipStream_t st = (hipStream_t)stream;
-  switch (grid->num_features / 3) {
-    case 1: hipLaunchKernelGGL((render_emit_direct_pair_kernel<1>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-    case 4: hipLaunchKernelGGL((render_emit_direct_pair_kernel<4>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-    case 9: hipLaunchKernelGGL((render_emit_direct_pair_kernel<9>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-    default: hipLaunchKernelGGL((render_emit_direct_pair_kernel<16>), dim3(blocks), dim3(kBlock), 0, st, g, p); break;
-  }
-  return launch_status();
+  return dispatch_sh(grid->num_features / 3, ShAll{}, [&](auto k) {
+    hipLaunchKernelGGL((render_emit_direct_pair_kernel<decltype(k)::value>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
+    return launch_status();
+  });
 }
 
 int rf_render_forward_pair(const RFGrid* grid, const RFRayBatch* rays, const uint32_t* flags, const RFRenderOut* outs, void* stream) {
@@ -4931,18 +4943,9 @@ int rf_render_backward_emit_direct(const RFGrid* grid, const RFRayBatch* rays, u
                                    const RFRenderGrads* grads, int32_t brick_size, int32_t* cursor_dev,
                                    float* records_sorted_dev, int32_t* hist_clear_dev, void* stream) {
   if (!grid) return RF_ERR_NULL_POINTER;
-  if (!cursor_dev || !records_sorted_dev) return RF_ERR_NULL_POINTER;
-  int shift, nb[3];
-  const int rc = brick_geometry(grid, brick_size, &shift, nb, false);
+  GradArgs gr;
+  const int rc = emit_direct_args(grid, brick_size, cursor_dev, records_sorted_dev, hist_clear_dev, &gr);
   if (rc != RF_OK) return rc;
-  GradArgs gr = {};
-  gr.cursor = cursor_dev;
-  gr.sorted = reinterpret_cast<float4*>(records_sorted_dev);
-  gr.hist_clear = hist_clear_dev;
-  gr.nkeys = nb[0] * nb[1] * nb[2] * 8;
-  gr.brick_shift = shift;
-  gr.nby = nb[1];
-  gr.nbz = nb[2];
   return backward_impl(grid, rays, flags, fwd, grads, gr, stream);
 }
 
@@ -5025,8 +5028,12 @@ int rf_scatter_records(const RFGrid* grid, const int16_t* keys_dev, const float*
 int32_t rf_expanded_record_floats(int32_t num_features) { return 4 * record_quads(num_features / 3); }
 
 extern "C++" {
-template <int K, bool ADAM, bool ONE_ROUND = false, bool SPLIT = false, int BX = 8, bool MIRROR = false>
-static int launch_gather(const GridArgs& g, const BrickArgs& a, int nbricks, float* gd, float* gf, hipStream_t st) {
+// a brick_gather_kernel variant: every template parameter but K
+template <bool ADAM, bool ONE_ROUND = false, bool SPLIT = false, int BX = 8, bool MIRROR = false>
+struct Gather {};
+
+template <int K, bool ADAM, bool ONE_ROUND, bool SPLIT, int BX, bool MIRROR>
+static int launch_gather(Gather<ADAM, ONE_ROUND, SPLIT, BX, MIRROR>, const GridArgs& g, const BrickArgs& a, int nbricks, float* gd, float* gf, hipStream_t st) {
   const int B = 1 << a.shift;
   const size_t lds = (size_t)gather_lds_words(B, 3 * K + 1, BX) * sizeof(float);
   if (lds > 150 * 1024) return RF_ERR_UNSUPPORTED;
@@ -5045,6 +5052,8 @@ static int launch_gather(const GridArgs& g, const BrickArgs& a, int nbricks, flo
 }
 }  // extern "C++"
 
+static unsigned long long max_stride(const RFGrid* g) { return (unsigned long long)(g->density_stride > g->feature_stride ? g->density_stride : g->feature_stride); }
+
 // what the optimizer in the brick flush needs of the grid and the state (checked before anything is launched)
 static int check_fused_adam(const RFGrid* grid, const RFAdamState* adam, int K, bool base_only) {
   // the update needs the complete gradient of every parameter in the owning workgroup: all channels covered by the lists
@@ -5056,28 +5065,36 @@ static int check_fused_adam(const RFGrid* grid, const RFAdamState* adam, int K, 
   if (C > 4 && (!adam->param_second_dev || !adam->exp_avg_second_dev || !adam->exp_avg_sq_second_dev)) return RF_ERR_NULL_POINTER;
   if (adam->param_first_dev != grid->densities_dev || (C > 4 && adam->param_second_dev != grid->features_dev)) return RF_ERR_BAD_SHAPE;
   if (adam->step < 1) return RF_ERR_BAD_SHAPE;
-  {  // the flush keeps element offsets in 31 bits
-    unsigned long long nodes = 1;
-    for (int ax = 0; ax < 3; ++ax) nodes *= (unsigned long long)((grid->dims[ax] + 7) / 8 * 8);
-    const unsigned long long smax = (unsigned long long)(grid->density_stride > grid->feature_stride ? grid->density_stride : grid->feature_stride);
-    if (nodes * smax >= (1ull << 31)) return RF_ERR_UNSUPPORTED;
-  }
+  if (node_count(grid, true) * max_stride(grid) >= (1ull << 31)) return RF_ERR_UNSUPPORTED;  // the flush keeps element offsets in 31 bits
   const uintptr_t align = (uintptr_t)adam->param_first_dev | (uintptr_t)adam->exp_avg_first_dev | (uintptr_t)adam->exp_avg_sq_first_dev |
                           (C > 4 ? ((uintptr_t)adam->param_second_dev | (uintptr_t)adam->exp_avg_second_dev | (uintptr_t)adam->exp_avg_sq_second_dev) : 0);
   if (align & 15u) return RF_ERR_BAD_SHAPE;
   return RF_OK;
 }
 
-static int brick_accumulate_impl(const RFGrid* grid, int32_t brick_size, const RFBrickList* lists, int32_t num_lists,
-                                 float* grad_densities_dev, float* grad_features_dev, int32_t accumulate,
-                                 const RFAdamState* adam, int32_t first_brick, int32_t num_bricks, void* stream, int32_t parts = 1,
-                                 void* scratch_dev = nullptr, int64_t scratch_bytes = 0) {
+// one brick pass as the rf_brick_accumulate* entry points ask for it (they check their own arguments first)
+struct BrickRequest {
+  float* grad_densities = nullptr;  // without `adam`: the gradient tensors; with it: the reference-layout mirror of the updated
+  float* grad_features = nullptr;   // parameters (4 x 8 x 8 bricks only), or null
+  int32_t accumulate = 0;
+  const RFAdamState* adam = nullptr;
+  int32_t first_brick = 0, num_bricks = 0;  // (num_bricks 0: all bricks from first_brick on)
+  int32_t parts = 1;                        // workgroups per brick; above 1 they meet in `scratch`
+  void* scratch = nullptr;
+  int64_t scratch_bytes = 0;
+};
+
+static int brick_accumulate_impl(const RFGrid* grid, int32_t brick_size, const RFBrickList* lists, int32_t num_lists, const BrickRequest& req,
+                                 void* stream) {
   int rc = check_grid(grid);
   if (rc != RF_OK) return rc;
   if (!lists) return RF_ERR_NULL_POINTER;
+  const RFAdamState* adam = req.adam;
+  float* const gd = req.grad_densities;
+  float* const gf = req.grad_features;
   if (!adam) {
-    if (!grad_densities_dev) return RF_ERR_NULL_POINTER;
-    if (!grad_features_dev && !(grid->layout != RF_LAYOUT_REFERENCE && grid->num_features == 3)) return RF_ERR_NULL_POINTER;
+    if (!gd) return RF_ERR_NULL_POINTER;
+    if (!gf && !second_tensor_optional(grid)) return RF_ERR_NULL_POINTER;
   }
   if (num_lists < 1 || num_lists > 2 * kMaxListsPerKind) return RF_ERR_BAD_SHAPE;
   int shift, nb[3];
@@ -5110,17 +5127,19 @@ static int brick_accumulate_impl(const RFGrid* grid, int32_t brick_size, const R
   a.nbx = nb[0];
   a.nby = nb[1];
   a.nbz = nb[2];
-  a.accumulate = accumulate;
+  a.accumulate = req.accumulate;
   const GridArgs g = to_args(grid);
   const int all_bricks = nb[0] * nb[1] * nb[2];
-  if (first_brick < 0 || num_bricks < 0 || first_brick + num_bricks > all_bricks) return RF_ERR_BAD_SHAPE;
-  const int nbricks = num_bricks > 0 ? num_bricks : all_bricks - first_brick;
-  a.brick_first = first_brick;
+  if (req.first_brick < 0 || req.num_bricks < 0 || req.first_brick + req.num_bricks > all_bricks) return RF_ERR_BAD_SHAPE;
+  const int nbricks = req.num_bricks > 0 ? req.num_bricks : all_bricks - req.first_brick;
+  a.brick_first = req.first_brick;
   if (nbricks == 0) return RF_OK;
-  hipStream_t st = (hipStream_t)stream;
   const int K = base_only ? 1 : grid->num_features / 3;
-  if (adam) {
-    if (accumulate) return RF_ERR_UNSUPPORTED;
+  // brick_gather_kernel<K, ...> for this pass's K out of `degrees`, the instantiations that exist of `variant`
+  auto gather = [&](auto k, auto variant) { return launch_gather<decltype(k)::value>(variant, g, a, nbricks, gd, gf, (hipStream_t)stream); };
+  auto launch = [&](auto degrees, auto variant) { return dispatch_sh(K, degrees, [&](auto k) { return gather(k, variant); }); };
+  if (adam) {  // (the optimizer in the flush exists for SH degree 0 / 2: check_fused_adam refuses the others)
+    if (req.accumulate) return RF_ERR_UNSUPPORTED;
     rc = check_fused_adam(grid, adam, K, base_only);
     if (rc != RF_OK) return rc;
     const double bc1 = 1.0 - pow((double)adam->beta1, (double)adam->step);
@@ -5136,93 +5155,80 @@ static int brick_accumulate_impl(const RFGrid* grid, int32_t brick_size, const R
     a.adam.b2 = adam->beta2;
     a.adam.eps = adam->eps;
     a.adam.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    {
-      unsigned long long nodes = 1;
-      for (int ax = 0; ax < 3; ++ax) nodes *= (unsigned long long)((grid->dims[ax] + 7) / 8 * 8);
-      const unsigned long long smax = (unsigned long long)(grid->density_stride > grid->feature_stride ? grid->density_stride : grid->feature_stride);
-      a.adam.byte_offsets_fit_32_bits = nodes * smax < (1ull << 30) && nodes <= (1ull << 24) && smax < (1ull << 24);
-    }
+    const unsigned long long nodes = node_count(grid, true), smax = max_stride(grid);
+    a.adam.byte_offsets_fit_32_bits = nodes * smax < (1ull << 30) && nodes <= (1ull << 24) && smax < (1ull << 24);
 #if defined(RF_BRICK_PROFILE) || defined(RF_BRICK_ABLATE)
-    {
-      const char* e = getenv("RF_BRICK_STAGGER");
-      a.stagger = e ? atoi(e) : 0;
-    }
+    a.stagger = env_int("RF_BRICK_STAGGER", 0);
 #endif
     const bool one_round = a.adam.byte_offsets_fit_32_bits && shift == 3;
     if (slab4) {  // 4 x 8 x 8 bricks: the 256-thread workgroups of the single-GPU optimizer pass
-      if (!one_round || parts > 1 || (K != 1 && K != 9)) return RF_ERR_UNSUPPORTED;
-      if (grad_densities_dev) {  // rf_brick_accumulate_adam_mirror: the updated parameters also in the reference layout
-        if (!grad_features_dev || (grid->dims[0] & 3) || (grid->dims[1] & 7) || (grid->dims[2] & 7) || g.bricked || first_brick != 0 || nbricks != nb[0] * nb[1] * nb[2])
+      if (!one_round || req.parts > 1 || (K != 1 && K != 9)) return RF_ERR_UNSUPPORTED;
+      if (gd) {  // rf_brick_accumulate_adam_mirror: the updated parameters also in the reference layout
+        if (!gf || (grid->dims[0] & 3) || (grid->dims[1] & 7) || (grid->dims[2] & 7) || g.bricked || req.first_brick != 0 || nbricks != all_bricks)
           return RF_ERR_UNSUPPORTED;
-        if ((reinterpret_cast<uintptr_t>(grad_densities_dev) | reinterpret_cast<uintptr_t>(grad_features_dev)) & 15u) return RF_ERR_BAD_SHAPE;
-        return K == 1 ? launch_gather<1, true, true, false, 4, true>(g, a, nbricks, grad_densities_dev, grad_features_dev, st)
-                      : launch_gather<9, true, true, false, 4, true>(g, a, nbricks, grad_densities_dev, grad_features_dev, st);
+        if ((reinterpret_cast<uintptr_t>(gd) | reinterpret_cast<uintptr_t>(gf)) & 15u) return RF_ERR_BAD_SHAPE;
+        return launch(ShEven{}, Gather<true, true, false, 4, true>{});
       }
-      return K == 1 ? launch_gather<1, true, true, false, 4>(g, a, nbricks, nullptr, nullptr, st) : launch_gather<9, true, true, false, 4>(g, a, nbricks, nullptr, nullptr, st);
+      return launch(ShEven{}, Gather<true, true, false, 4>{});
     }
-    if (grad_densities_dev) return RF_ERR_UNSUPPORTED;  // (the mirror write-out exists for the 4 x 8 x 8 pass only)
-    if (parts > 1) {  // several workgroups per brick (rf_brick_accumulate_adam_split)
+    if (gd) return RF_ERR_UNSUPPORTED;  // (the mirror write-out exists for the 4 x 8 x 8 pass only)
+    if (req.parts > 1) {  // several workgroups per brick (rf_brick_accumulate_adam_split)
       if (!one_round) return RF_ERR_UNSUPPORTED;
-      if (parts > kMaxListsPerKind || !scratch_dev) return parts > kMaxListsPerKind ? RF_ERR_BAD_SHAPE : RF_ERR_NULL_POINTER;
+      if (req.parts > kMaxListsPerKind || !req.scratch) return req.parts > kMaxListsPerKind ? RF_ERR_BAD_SHAPE : RF_ERR_NULL_POINTER;
       const long long words = brick_acc_words(8, 3 * K + 1);
-      const long long state_bytes = ((long long)nbricks * (1 + parts) * 4 + 255) / 256 * 256;
-      if (scratch_bytes < state_bytes + (long long)nbricks * parts * words * 4 || ((uintptr_t)scratch_dev & 15u)) return RF_ERR_BAD_SHAPE;
-      a.parts = parts;
-      a.part_state = reinterpret_cast<int*>(scratch_dev);
-      a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch_dev) + state_bytes);
-      return K == 1 ? launch_gather<1, true, true, true>(g, a, nbricks, nullptr, nullptr, st) : launch_gather<9, true, true, true>(g, a, nbricks, nullptr, nullptr, st);
+      const long long state_bytes = ((long long)nbricks * (1 + req.parts) * 4 + 255) / 256 * 256;
+      if (req.scratch_bytes < state_bytes + (long long)nbricks * req.parts * words * 4 || ((uintptr_t)req.scratch & 15u)) return RF_ERR_BAD_SHAPE;
+      a.parts = req.parts;
+      a.part_state = reinterpret_cast<int*>(req.scratch);
+      a.partial = reinterpret_cast<float*>(reinterpret_cast<char*>(req.scratch) + state_bytes);
+      return launch(ShEven{}, Gather<true, true, true>{});
     }
-    switch (K) {
-      case 1:
-        return one_round ? launch_gather<1, true, true>(g, a, nbricks, nullptr, nullptr, st) : launch_gather<1, true, false>(g, a, nbricks, nullptr, nullptr, st);
-      default:
-        return one_round ? launch_gather<9, true, true>(g, a, nbricks, nullptr, nullptr, st) : launch_gather<9, true, false>(g, a, nbricks, nullptr, nullptr, st);
-    }
+    return dispatch_sh(K, ShEven{}, [&](auto k) { return one_round ? gather(k, Gather<true, true>{}) : gather(k, Gather<true, false>{}); });
   }
   if (slab4) {  // 4 x 8 x 8 bricks into gradient tensors: SH degree 0 / 2 (the lists of a deferred gradient bucket, summed on demand)
     if (K != 1 && K != 9) return RF_ERR_UNSUPPORTED;
-    return K == 1 ? launch_gather<1, false, true, false, 4>(g, a, nbricks, grad_densities_dev, grad_features_dev, st)
-                  : launch_gather<9, false, true, false, 4>(g, a, nbricks, grad_densities_dev, grad_features_dev, st);
+    return launch(ShEven{}, Gather<false, true, false, 4>{});
   }
-  switch (K) {
-    case 1:
-      return shift == 3 ? launch_gather<1, false, true>(g, a, nbricks, grad_densities_dev, grad_features_dev, st)
-                        : launch_gather<1, false, false>(g, a, nbricks, grad_densities_dev, grad_features_dev, st);
-    case 4:
-      return shift == 3 ? launch_gather<4, false, true>(g, a, nbricks, grad_densities_dev, grad_features_dev, st)
-                        : launch_gather<4, false, false>(g, a, nbricks, grad_densities_dev, grad_features_dev, st);
-    case 9:
-      return shift == 3 ? launch_gather<9, false, true>(g, a, nbricks, grad_densities_dev, grad_features_dev, st)
-                        : launch_gather<9, false, false>(g, a, nbricks, grad_densities_dev, grad_features_dev, st);
-    default:
-      return shift == 3 ? launch_gather<16, false, true>(g, a, nbricks, grad_densities_dev, grad_features_dev, st)
-                        : launch_gather<16, false, false>(g, a, nbricks, grad_densities_dev, grad_features_dev, st);
-  }
+  return dispatch_sh(K, ShAll{}, [&](auto k) { return shift == 3 ? gather(k, Gather<false, true>{}) : gather(k, Gather<false, false>{}); });
 }
 
 int rf_brick_accumulate(const RFGrid* grid, int32_t brick_size, const RFBrickList* lists, int32_t num_lists,
                         float* grad_densities_dev, float* grad_features_dev, int32_t accumulate, void* stream) {
-  return brick_accumulate_impl(grid, brick_size, lists, num_lists, grad_densities_dev, grad_features_dev, accumulate, nullptr, 0, 0, stream);
+  BrickRequest req;
+  req.grad_densities = grad_densities_dev;
+  req.grad_features = grad_features_dev;
+  req.accumulate = accumulate;
+  return brick_accumulate_impl(grid, brick_size, lists, num_lists, req, stream);
 }
 
 int rf_brick_accumulate_adam(const RFGrid* grid, int32_t brick_size, const RFBrickList* lists, int32_t num_lists,
                              const RFAdamState* adam, void* stream) {
   if (!adam) return RF_ERR_NULL_POINTER;
-  return brick_accumulate_impl(grid, brick_size, lists, num_lists, nullptr, nullptr, 0, adam, 0, 0, stream);
+  BrickRequest req;
+  req.adam = adam;
+  return brick_accumulate_impl(grid, brick_size, lists, num_lists, req, stream);
 }
 
 int rf_brick_accumulate_adam_mirror(const RFGrid* grid, int32_t brick_size, const RFBrickList* lists, int32_t num_lists,
                                     const RFAdamState* adam, float* mirror_densities_dev, float* mirror_features_dev, void* stream) {
   if (!adam || !mirror_densities_dev || !mirror_features_dev) return RF_ERR_NULL_POINTER;
   if (brick_size != RF_BRICK_4X8X8) return RF_ERR_UNSUPPORTED;
-  return brick_accumulate_impl(grid, brick_size, lists, num_lists, mirror_densities_dev, mirror_features_dev, 0, adam, 0, 0, stream);
+  BrickRequest req;
+  req.adam = adam;
+  req.grad_densities = mirror_densities_dev;
+  req.grad_features = mirror_features_dev;
+  return brick_accumulate_impl(grid, brick_size, lists, num_lists, req, stream);
 }
 
 int rf_brick_accumulate_adam_range(const RFGrid* grid, int32_t brick_size, const RFBrickList* lists, int32_t num_lists,
                                    const RFAdamState* adam, int32_t first_brick, int32_t num_bricks, void* stream) {
   if (!adam) return RF_ERR_NULL_POINTER;
   if (num_bricks < 1) return num_bricks == 0 ? RF_OK : RF_ERR_BAD_SHAPE;
-  return brick_accumulate_impl(grid, brick_size, lists, num_lists, nullptr, nullptr, 0, adam, first_brick, num_bricks, stream);
+  BrickRequest req;
+  req.adam = adam;
+  req.first_brick = first_brick;
+  req.num_bricks = num_bricks;
+  return brick_accumulate_impl(grid, brick_size, lists, num_lists, req, stream);
 }
 
 int64_t rf_brick_split_scratch_bytes(const RFGrid* grid, int32_t num_bricks, int32_t parts) {
@@ -5238,7 +5244,14 @@ int rf_brick_accumulate_adam_split(const RFGrid* grid, int32_t brick_size, const
   if (!adam) return RF_ERR_NULL_POINTER;
   if (num_bricks < 1) return num_bricks == 0 ? RF_OK : RF_ERR_BAD_SHAPE;
   if (parts < 1) return RF_ERR_BAD_SHAPE;
-  return brick_accumulate_impl(grid, brick_size, lists, num_lists, nullptr, nullptr, 0, adam, first_brick, num_bricks, stream, parts, scratch_dev, scratch_bytes);
+  BrickRequest req;
+  req.adam = adam;
+  req.first_brick = first_brick;
+  req.num_bricks = num_bricks;
+  req.parts = parts;
+  req.scratch = scratch_dev;
+  req.scratch_bytes = scratch_bytes;
+  return brick_accumulate_impl(grid, brick_size, lists, num_lists, req, stream);
 }
 
 int rf_grid_query(const RFGrid* grid, const float* points_dev, int64_t num_points, float* out_dev, void* stream) {
@@ -5260,7 +5273,7 @@ int rf_grid_query_backward(const RFGrid* grid, const float* points_dev, int64_t 
   if (rc != RF_OK) return rc;
   if (num_points == 0) return RF_OK;
   if (!points_dev || !grad_out_dev || !grad_densities_dev) return RF_ERR_NULL_POINTER;
-  if (!grad_features_dev && !(grid->layout != RF_LAYOUT_REFERENCE && grid->num_features == 3)) return RF_ERR_NULL_POINTER;
+  if (!grad_features_dev && !second_tensor_optional(grid)) return RF_ERR_NULL_POINTER;
   if (num_points < 0) return RF_ERR_BAD_SHAPE;
   const GridArgs g = to_args(grid);
   const long long total = (long long)num_points * (g.F + 1);
@@ -5292,31 +5305,19 @@ int rf_render_backward_rays(const RFGrid* grid, const RFRayBatch* rays, uint32_t
   if (!fwd || !grads) return RF_ERR_NULL_POINTER;
   if (rays->camera) return RF_ERR_UNSUPPORTED;
   if (rays->num_rays == 0 || (!grad_origins_dev && !grad_directions_dev)) return RF_OK;
-  if (!fwd->sample_cache_dev || !fwd->trans_cache_dev || !fwd->stop_cache_dev || !fwd->chunk_mask_dev) return RF_ERR_NULL_POINTER;
+  if (!has_caches(fwd)) return RF_ERR_NULL_POINTER;
   if (!grid->features_dev && grid->num_features > 3) return RF_ERR_NULL_POINTER;
   const GridArgs g = to_args(grid);
   const RayArgs r = to_args(rays, flags);
   const OutArgs o = to_args(fwd);
   GradArgs gr = {};
-  gr.gcolour = grads->grad_colour_dev;
-  gr.gdepth = grads->grad_depth_dev;
-  gr.gacc = grads->grad_acc_dev;
+  set_grads(grads, &gr);
   const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
-  hipStream_t st = (hipStream_t)stream;
-  const bool diffuse = flags & RF_FLAG_RENDER_DIFFUSE;
-  const int K = grid->num_features / 3;
-#define RF_RAYS_LAUNCH(K_, D_) \
-  hipLaunchKernelGGL((render_backward_rays_kernel<K_, D_>), dim3(blocks), dim3(kBlock), 0, st, g, r, o, gr, flags, grad_origins_dev, grad_directions_dev)
-  if (diffuse || K == 1)
-    RF_RAYS_LAUNCH(1, true);
-  else if (K == 4)
-    RF_RAYS_LAUNCH(4, false);
-  else if (K == 9)
-    RF_RAYS_LAUNCH(9, false);
-  else
-    RF_RAYS_LAUNCH(16, false);
-#undef RF_RAYS_LAUNCH
-  return launch_status();
+  return dispatch_render(grid->num_features / 3, flags & RF_FLAG_RENDER_DIFFUSE, [&](auto k, auto d) {
+    hipLaunchKernelGGL((render_backward_rays_kernel<decltype(k)::value, decltype(d)::value>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, o, gr, flags,
+                       grad_origins_dev, grad_directions_dev);
+    return launch_status();
+  });
 }
 
 int rf_build_occupancy(const RFGrid* grid, float threshold, uint32_t* occupancy_dev, void* stream) {
@@ -5363,11 +5364,10 @@ int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream) {
     float4* base = reinterpret_cast<float4*>(const_cast<float*>(dst->densities_dev));
     float4* rest = reinterpret_cast<float4*>(const_cast<float*>(dst->features_dev));
     const unsigned blocks = grid_1d((long long)nodes * ((gd.F + 1) / 4), 256, 256LL * 64);
-    if (K == 1)
-      hipLaunchKernelGGL((reference_to_split_kernel<1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, gs.dens, gs.feat, gs.dstride, gs.fstride, base, rest, nodes);
-    else
-      hipLaunchKernelGGL((reference_to_split_kernel<9>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, gs.dens, gs.feat, gs.dstride, gs.fstride, base, rest, nodes);
-    return launch_status();
+    return dispatch_sh(K, ShEven{}, [&](auto k) {
+      hipLaunchKernelGGL((reference_to_split_kernel<decltype(k)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, gs.dens, gs.feat, gs.dstride, gs.fstride, base, rest, nodes);
+      return launch_status();
+    });
   }
   if (src->layout == RF_LAYOUT_SPLIT && dst->layout == RF_LAYOUT_REFERENCE && (K == 1 || K == 9) && src->density_stride == 4 &&
       (K == 1 || src->feature_stride == gd.F - 3) && (((uintptr_t)src->densities_dev | (uintptr_t)src->features_dev) & 15u) == 0 &&
@@ -5379,20 +5379,17 @@ int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream) {
     if (dst->density_stride == 1 && dst->feature_stride == gd.F && (nodes & 3u) == 0 && (((uintptr_t)dd | (uintptr_t)df) & 15u) == 0 &&
         (unsigned long long)nodes * (unsigned long long)gd.F < (1ull << 32)) {  // contiguous reference tensors: 16-byte stores
       const unsigned blocks4 = grid_1d((long long)nodes * gd.F / 4 + nodes / 4, 256, 256LL * 64);
-      if (K == 1)
-        hipLaunchKernelGGL((split_to_reference_quads_kernel<1>), dim3(blocks4), dim3(256), 0, (hipStream_t)stream, src->densities_dev, src->features_dev,
+      return dispatch_sh(K, ShEven{}, [&](auto k) {
+        hipLaunchKernelGGL((split_to_reference_quads_kernel<decltype(k)::value>), dim3(blocks4), dim3(256), 0, (hipStream_t)stream, src->densities_dev, src->features_dev,
                            reinterpret_cast<float4*>(dd), reinterpret_cast<float4*>(df), nodes);
-      else
-        hipLaunchKernelGGL((split_to_reference_quads_kernel<9>), dim3(blocks4), dim3(256), 0, (hipStream_t)stream, src->densities_dev, src->features_dev,
-                           reinterpret_cast<float4*>(dd), reinterpret_cast<float4*>(df), nodes);
-      return launch_status();
+        return launch_status();
+      });
     }
     const unsigned blocks = grid_1d((long long)nodes * ((gd.F + 1) / 4), 256, 256LL * 64);
-    if (K == 1)
-      hipLaunchKernelGGL((split_to_reference_kernel<1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, rest, dd, df, gd.dstride, gd.fstride, nodes);
-    else
-      hipLaunchKernelGGL((split_to_reference_kernel<9>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, rest, dd, df, gd.dstride, gd.fstride, nodes);
-    return launch_status();
+    return dispatch_sh(K, ShEven{}, [&](auto k) {
+      hipLaunchKernelGGL((split_to_reference_kernel<decltype(k)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, rest, dd, df, gd.dstride, gd.fstride, nodes);
+      return launch_status();
+    });
   }
   const int cw = gd.F + 1 <= 32 ? 32 : 64, per_block = 256 / cw;
   hipLaunchKernelGGL(convert_grid_kernel, dim3(grid_1d(nodes, per_block, 256LL * 256)), dim3(cw, per_block), 0, (hipStream_t)stream, gs, gd,
@@ -5486,10 +5483,10 @@ int rf_train_step(const RFGrid* grid, const RFTrainStep* step, void* stream) {
     if (step->adam) {
       rc = check_fused_adam(grid, step->adam, grid->num_features / 3, false);
       if (rc != RF_OK) return rc;
-    } else if (!step->grad_first_dev || (!step->grad_second_dev && !(grid->layout != RF_LAYOUT_REFERENCE && grid->num_features == 3))) {
+    } else if (!step->grad_first_dev || (!step->grad_second_dev && !second_tensor_optional(grid))) {
       return RF_ERR_NULL_POINTER;
     }
-    }
+  }
   const float loss_scale = step->loss_scale != 0.0f ? step->loss_scale : 1.0f;
   hipStream_t st = (hipStream_t)stream;
   int ev = 0;
@@ -5541,15 +5538,18 @@ int rf_train_step(const RFGrid* grid, const RFTrainStep* step, void* stream) {
                        step->pixels_dev, n3, loss_scale / (float)n3, loss_blocks, bl, nkeys, offset_blocks, passes);
     return launch_status();
   };
+  auto emit_direct = [&](int i) -> int {  // the adjoint of render i, its records straight into the sorted list
+    const RFPassScratch& ps = step->pass[i];
+    const RFRenderGrads grads = {ps.grad_colour_dev, nullptr, nullptr};
+    return rf_render_backward_emit_direct(grid, &rays[i], flags[i], &ps.out, &grads, ps.out.brick_size, ps.cursor_dev, ps.records_sorted_dev,
+                                          ps.out.key_hist_dev, stream);
+  };
   if (run_forward) {
     RF_STEP_EVENT();
     rc = launch_select();
     if (rc != RF_OK) return rc;
     RF_STEP_EVENT();
-    static const bool pair_forwards = [] {
-      const char* e = getenv("RF_FWD_PAIR");
-      return e ? atoi(e) != 0 : true;
-    }();
+    static const bool pair_forwards = env_flag("RF_FWD_PAIR", true);
     bool paired = false;
     if (pair_forwards) {  // both renders in one launch: the second finds the base records of its corners on chip
       const RFRayBatch* const rr[2] = {&rays[0], &rays[1]};
@@ -5592,9 +5592,7 @@ int rf_train_step(const RFGrid* grid, const RFTrainStep* step, void* stream) {
       if (rc != RF_OK) return rc;
       rc = launch_losses_and_offsets(2);
       if (rc != RF_OK) return rc;
-      const RFPassScratch& ps = step->pass[1];
-      const RFRenderGrads grads = {ps.grad_colour_dev, nullptr, nullptr};
-      rc = rf_render_backward_emit_direct(grid, &rays[1], flags[1], &ps.out, &grads, ps.out.brick_size, ps.cursor_dev, ps.records_sorted_dev, ps.out.key_hist_dev, stream);
+      rc = emit_direct(1);
       if (rc != RF_OK) return rc;
     }
     if (step->phases & RF_STEP_SPECULAR_FORWARD) {
@@ -5605,10 +5603,7 @@ int rf_train_step(const RFGrid* grid, const RFTrainStep* step, void* stream) {
     }
   }
   if (emit_one[0] || emit_one[1]) {
-    static const bool pair_emits = [] {
-      const char* e = getenv("RF_EMIT_PAIR");
-      return e ? atoi(e) != 0 : true;
-    }();
+    static const bool pair_emits = env_flag("RF_EMIT_PAIR", true);
     bool paired = false;
     if (pair_emits && emit_one[0] && emit_one[1]) {
       RF_STEP_EVENT();
@@ -5627,11 +5622,8 @@ int rf_train_step(const RFGrid* grid, const RFTrainStep* step, void* stream) {
     }
     for (int i = 0; i < 2 && !paired; ++i) {
       if (!emit_one[i]) continue;
-      const RFPassScratch& ps = step->pass[i];
-      const RFRenderGrads grads = {ps.grad_colour_dev, nullptr, nullptr};
       RF_STEP_EVENT();  // (offsets[0] = the launch above, offsets[1] = nothing)
-      rc = rf_render_backward_emit_direct(grid, &rays[i], flags[i], &ps.out, &grads, ps.out.brick_size, ps.cursor_dev, ps.records_sorted_dev,
-                                          ps.out.key_hist_dev, stream);
+      rc = emit_direct(i);
       if (rc != RF_OK) return rc;
       RF_STEP_EVENT();
     }

@@ -129,6 +129,11 @@ def _variant(grid: "VoxelGrid", flags: int) -> str:
     return "diffuse" if (flags & _lib.FLAG_RENDER_DIFFUSE) else f"sh{grid.sh_degree}"
 
 
+def _list_label(grid: "VoxelGrid", render_diffuse) -> str:
+    """span label of a pass over record lists (base-channel records: "diffuse")"""
+    return "diffuse" if render_diffuse or grid.sh_degree == 0 else "sh" + str(grid.sh_degree)
+
+
 def _stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
@@ -189,6 +194,34 @@ def _ray_batch(origins: Tensor, directions: Tensor, num_samples: int, near: floa
     return rb, tv
 
 
+def _fill_caches(out, caches):
+    """the sample cache of a saving forward render (sample_cache, trans_cache, stop, chunk_mask) into an RFRenderOut"""
+    out.sample_cache_dev, out.trans_cache_dev, out.stop_cache_dev, out.chunk_mask_dev = (t.data_ptr() for t in caches)
+    return out
+
+
+def _render_grads(g_colour: Optional[Tensor], g_depth: Optional[Tensor], g_acc: Optional[Tensor]):
+    grads = _lib.RFRenderGrads()
+    grads.grad_colour_dev, grads.grad_depth_dev, grads.grad_acc_dev = _ptr(g_colour), _ptr(g_depth), _ptr(g_acc)
+    return grads
+
+
+def _render_out(n: int, num_samples: int, dev, save: bool, key_hist: Optional[Tensor] = None, brick_size: int = 8):
+    """fresh output (and cache) tensors of one render + their RFRenderOut"""
+    f32 = dict(dtype=torch.float32, device=dev)
+    colour, depth, acc, disparity = torch.empty((n, 3), **f32), torch.empty((n, 1), **f32), torch.empty((n, 1), **f32), torch.empty((n, 1), **f32)
+    out = _lib.RFRenderOut()
+    out.colour_dev, out.depth_dev, out.acc_dev, out.disparity_dev = colour.data_ptr(), depth.data_ptr(), acc.data_ptr(), disparity.data_ptr()
+    caches = None
+    if save:
+        caches = (torch.empty((n, num_samples, 4), **f32), torch.empty((n, num_samples), **f32), torch.empty((n,), dtype=torch.int32, device=dev),
+                  torch.empty((n, (num_samples + 63) // 64), dtype=torch.int64, device=dev))
+        _fill_caches(out, caches)
+        if key_hist is not None:
+            out.key_hist_dev, out.brick_size = key_hist.data_ptr(), int(brick_size)
+    return (colour, depth, acc, disparity), caches, out
+
+
 def render_forward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_rand: Optional[Tensor], num_samples: int,
                        near: float, far: float, flags: int, save: bool, key_hist: Optional[Tensor] = None, brick_size: int = 8):
     """Enqueue rf_render_forward.  Returns (colour [N,3], depth [N,1], acc [N,1], disparity [N,1], caches) where
@@ -203,26 +236,11 @@ def render_forward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_r
     dev = origins.device
     rf_grid = grid.forward_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))  # (reference storage: its split shadow)
     rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    colour = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    acc = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    disparity = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    out = _lib.RFRenderOut()
-    out.colour_dev, out.depth_dev, out.acc_dev, out.disparity_dev = colour.data_ptr(), depth.data_ptr(), acc.data_ptr(), disparity.data_ptr()
-    caches = None
-    if save:
-        cache = torch.empty((n, num_samples, 4), dtype=torch.float32, device=dev)
-        tcache = torch.empty((n, num_samples), dtype=torch.float32, device=dev)
-        stop = torch.empty((n,), dtype=torch.int32, device=dev)
-        cmask = torch.empty((n, (num_samples + 63) // 64), dtype=torch.int64, device=dev)
-        out.sample_cache_dev, out.trans_cache_dev, out.stop_cache_dev, out.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
-        caches = (cache, tcache, stop, cmask)
-        if key_hist is not None:
-            out.key_hist_dev, out.brick_size = key_hist.data_ptr(), int(brick_size)
+    tensors, caches, out = _render_out(n, num_samples, dev, save, key_hist, brick_size)
     with _span(f"render_forward[{_variant(grid, flags)}{',save' if save else ''}]", dev):
         rc = lib.rf_render_forward(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(out), _stream(dev))
     _lib.check(rc, "rf_render_forward")
-    return colour, depth, acc, disparity, caches
+    return tensors + (caches,)
 
 
 def render_frame_raw(grid: VoxelGrid, height: int, width: int, focal: float, rotation, translation, num_samples: int, near: float, far: float,
@@ -254,16 +272,11 @@ def render_frame_raw(grid: VoxelGrid, height: int, width: int, focal: float, rot
         rb.jitter_key = int(jitter.key) & 0xFFFFFFFFFFFFFFFF
         flags = int(flags) | _lib.FLAG_JITTER_KEYED
     rf_grid = grid.forward_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
-    colour = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    acc = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    disparity = torch.empty((n, 1), dtype=torch.float32, device=dev)
-    out = _lib.RFRenderOut()
-    out.colour_dev, out.depth_dev, out.acc_dev, out.disparity_dev = colour.data_ptr(), depth.data_ptr(), acc.data_ptr(), disparity.data_ptr()
+    tensors, _, out = _render_out(n, num_samples, dev, save=False)
     with _span(f"render_forward[{_variant(grid, flags)},frame]", dev):
         rc = lib.rf_render_forward(C.byref(rf_grid), C.byref(rb), int(flags), C.byref(out), _stream(dev))
     _lib.check(rc, "rf_render_forward")
-    return colour, depth, acc, disparity
+    return tensors
 
 
 def render_backward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_rand: Optional[Tensor], num_samples: int,
@@ -275,11 +288,7 @@ def render_backward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_
     dev = origins.device
     rf_grid = grid.to_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
     rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads = _lib.RFRenderGrads()
-    grads.grad_colour_dev, grads.grad_depth_dev, grads.grad_acc_dev = _ptr(g_colour), _ptr(g_depth), _ptr(g_acc)
-    cache, tcache, stop, cmask = caches
-    fwd = _lib.RFRenderOut()
-    fwd.sample_cache_dev, fwd.trans_cache_dev, fwd.stop_cache_dev, fwd.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
+    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
     with _span(f"render_backward[{_variant(grid, flags)}]", dev):
         rc = lib.rf_render_backward(
             C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), grad_first.data_ptr(), _ptr(grad_second), _stream(dev)
@@ -297,11 +306,7 @@ def render_backward_rays_raw(grid: VoxelGrid, origins: Tensor, directions: Tenso
     n = origins.shape[0]
     rf_grid = grid.forward_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
     rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads = _lib.RFRenderGrads()
-    grads.grad_colour_dev, grads.grad_depth_dev, grads.grad_acc_dev = _ptr(g_colour), _ptr(g_depth), _ptr(g_acc)
-    cache, tcache, stop, cmask = caches
-    fwd = _lib.RFRenderOut()
-    fwd.sample_cache_dev, fwd.trans_cache_dev, fwd.stop_cache_dev, fwd.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
+    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
     go = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_origins else None
     gdir = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_directions else None
     with _span(f"render_backward_rays[{_variant(grid, flags)}]", dev):
@@ -334,11 +339,7 @@ def render_backward_emit_raw(grid: VoxelGrid, origins: Tensor, directions: Tenso
     dev = origins.device
     rf_grid = grid.to_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
     rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads = _lib.RFRenderGrads()
-    grads.grad_colour_dev, grads.grad_depth_dev, grads.grad_acc_dev = _ptr(g_colour), _ptr(g_depth), _ptr(g_acc)
-    cache, tcache, stop, cmask = caches
-    fwd = _lib.RFRenderOut()
-    fwd.sample_cache_dev, fwd.trans_cache_dev, fwd.stop_cache_dev, fwd.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
+    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
     with _span(f"render_backward_emit[{_variant(grid, flags)}]", dev):
         rc = lib.rf_render_backward_emit(
             C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), int(brick_size), keys.data_ptr(), records.data_ptr(),
@@ -357,33 +358,13 @@ def render_backward_emit_direct_raw(grid: VoxelGrid, origins: Tensor, directions
     dev = origins.device
     rf_grid = grid.to_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
     rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads = _lib.RFRenderGrads()
-    grads.grad_colour_dev, grads.grad_depth_dev, grads.grad_acc_dev = _ptr(g_colour), _ptr(g_depth), _ptr(g_acc)
-    cache, tcache, stop, cmask = caches
-    fwd = _lib.RFRenderOut()
-    fwd.sample_cache_dev, fwd.trans_cache_dev, fwd.stop_cache_dev, fwd.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
+    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
     with _span(f"render_backward_emit_direct[{_variant(grid, flags)}]", dev):
         rc = lib.rf_render_backward_emit_direct(
             C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), int(brick_size), cursor.data_ptr(),
             records_sorted.data_ptr(), _ptr(hist_clear), _stream(dev),
         )
     _lib.check(rc, "rf_render_backward_emit_direct")
-
-
-def _render_out(n: int, num_samples: int, dev, save: bool, key_hist: Optional[Tensor], brick_size: int):
-    """fresh output (and cache) tensors of one render + their RFRenderOut"""
-    f32 = dict(dtype=torch.float32, device=dev)
-    colour, depth, acc, disparity = torch.empty((n, 3), **f32), torch.empty((n, 1), **f32), torch.empty((n, 1), **f32), torch.empty((n, 1), **f32)
-    out = _lib.RFRenderOut()
-    out.colour_dev, out.depth_dev, out.acc_dev, out.disparity_dev = colour.data_ptr(), depth.data_ptr(), acc.data_ptr(), disparity.data_ptr()
-    caches = None
-    if save:
-        caches = (torch.empty((n, num_samples, 4), **f32), torch.empty((n, num_samples), **f32), torch.empty((n,), dtype=torch.int32, device=dev),
-                  torch.empty((n, (num_samples + 63) // 64), dtype=torch.int64, device=dev))
-        out.sample_cache_dev, out.trans_cache_dev, out.stop_cache_dev, out.chunk_mask_dev = (t.data_ptr() for t in caches)
-        if key_hist is not None:
-            out.key_hist_dev, out.brick_size = key_hist.data_ptr(), int(brick_size)
-    return (colour, depth, acc, disparity), caches, out
 
 
 def render_forward_pair_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_rands, num_samples: int, near: float, far: float, flags,
@@ -435,8 +416,7 @@ def render_backward_emit_direct_pair_raw(grid: VoxelGrid, origins: Tensor, direc
         keep.append(tv)
         rays[i], fl[i] = rb, _jitter_flags(flags[i], t_rands[i])
         ps = passes[i]
-        cache, tcache, stop, cmask = caches2[i]
-        ps.out.sample_cache_dev, ps.out.trans_cache_dev, ps.out.stop_cache_dev, ps.out.chunk_mask_dev = cache.data_ptr(), tcache.data_ptr(), stop.data_ptr(), cmask.data_ptr()
+        _fill_caches(ps.out, caches2[i])
         ps.out.key_hist_dev, ps.out.brick_size = hists[i].data_ptr(), int(brick_size)
         ps.grad_colour_dev, ps.cursor_dev, ps.offsets_dev, ps.records_sorted_dev = g_colours[i].data_ptr(), cursor2[i].data_ptr(), offsets2[i].data_ptr(), records2[i].data_ptr()
     with _span(f"render_backward_emit_direct[{_variant(grid, flags[0])}+diffuse]", dev):
@@ -494,11 +474,20 @@ def bin_records_by_brick(grid: VoxelGrid, keys: Tensor, records: Tensor, render_
         rc = lib.rf_bin_offsets(hist.data_ptr(), int(hist.numel()), offsets.data_ptr(), cursor.data_ptr(), _stream(dev))
     _lib.check(rc, "rf_bin_offsets")
     rf_grid = grid.to_rf_grid()
-    with _span(f"scatter_records[{'diffuse' if render_diffuse or grid.sh_degree == 0 else 'sh' + str(grid.sh_degree)}]", dev):
+    with _span(f"scatter_records[{_list_label(grid, render_diffuse)}]", dev):
         rc = lib.rf_scatter_records(C.byref(rf_grid), keys.data_ptr(), records.data_ptr(), keys.numel(), cursor.data_ptr(),
                                     int(bool(render_diffuse)), records_sorted.data_ptr(), hist.data_ptr(), int(hist.numel()), _stream(dev))
     _lib.check(rc, "rf_scatter_records")
     return offsets
+
+
+def _brick_lists(grid: VoxelGrid, lists):
+    """``lists`` = [(records_sorted, offsets, render_diffuse), ...] (the records a tensor or an int, a raw device address) as an
+    RFBrickList array, with the label of the pass's profiler span"""
+    arr = (_lib.RFBrickList * len(lists))()
+    for i, (rec, off, diffuse) in enumerate(lists):
+        arr[i].records_sorted_dev, arr[i].offsets_dev, arr[i].render_diffuse = (rec if isinstance(rec, int) else rec.data_ptr()), off.data_ptr(), int(bool(diffuse))
+    return arr, _list_label(grid, lists[0][2])
 
 
 def brick_accumulate_raw(grid: VoxelGrid, brick_size: int, lists, grad_first: Tensor, grad_second: Optional[Tensor],
@@ -507,11 +496,9 @@ def brick_accumulate_raw(grid: VoxelGrid, brick_size: int, lists, grad_first: Te
     rf_brick_accumulate."""
     lib = _lib.load()
     dev = grad_first.device
-    arr = (_lib.RFBrickList * len(lists))()
-    for i, (rec, off, diffuse) in enumerate(lists):
-        arr[i].records_sorted_dev, arr[i].offsets_dev, arr[i].render_diffuse = rec.data_ptr(), off.data_ptr(), int(bool(diffuse))
+    arr, label = _brick_lists(grid, lists)
     rf_grid = grid.to_rf_grid()
-    with _span(f"brick_accumulate[{'diffuse' if lists[0][2] or grid.sh_degree == 0 else 'sh' + str(grid.sh_degree)}]", dev):
+    with _span(f"brick_accumulate[{label}]", dev):
         rc = lib.rf_brick_accumulate(C.byref(rf_grid), int(brick_size), arr, len(lists), grad_first.data_ptr(), _ptr(grad_second), int(bool(accumulate)), _stream(dev))
     _lib.check(rc, "rf_brick_accumulate")
 
@@ -532,9 +519,7 @@ def brick_accumulate_adam_raw(grid: VoxelGrid, brick_size: int, lists, exp_avg, 
     # (``_tensors``: no wait for parameters a data-parallel step left in flight -- that step orders its launches against them itself)
     first, second = (grid._tensors() if rf_grid is not None else grid.kernel_tensors()) if params is None else params
     dev = first.device
-    arr = (_lib.RFBrickList * len(lists))()
-    for i, (rec, off, diffuse) in enumerate(lists):
-        arr[i].records_sorted_dev, arr[i].offsets_dev, arr[i].render_diffuse = (rec if isinstance(rec, int) else rec.data_ptr()), off.data_ptr(), int(bool(diffuse))
+    arr, label = _brick_lists(grid, lists)
     st = _lib.RFAdamState()
     st.param_first_dev, st.param_second_dev = first.data_ptr(), _ptr(second)
     st.exp_avg_first_dev, st.exp_avg_second_dev = exp_avg[0].data_ptr(), _ptr(exp_avg[1])
@@ -542,7 +527,7 @@ def brick_accumulate_adam_raw(grid: VoxelGrid, brick_size: int, lists, exp_avg, 
     st.lr, st.beta1, st.beta2, st.eps, st.step = float(lr), float(beta1), float(beta2), float(eps), int(step)
     if rf_grid is None:
         rf_grid = grid.to_rf_grid()
-    with _span(f"brick_accumulate_adam[{'diffuse' if lists[0][2] or grid.sh_degree == 0 else 'sh' + str(grid.sh_degree)}]", dev):
+    with _span(f"brick_accumulate_adam[{label}]", dev):
         if mirror is not None:
             rc = lib.rf_brick_accumulate_adam_mirror(C.byref(rf_grid), int(brick_size), arr, len(lists), C.byref(st), mirror[0].data_ptr(), mirror[1].data_ptr(), _stream(dev))
         elif split is not None and int(split[0]) > 1:
@@ -634,6 +619,43 @@ def _return_hist(hist: Tensor) -> None:
         pool.append(hist)
 
 
+def _prep_grad(g: Optional[Tensor]) -> Optional[Tensor]:
+    return None if g is None else g.detach().to(torch.float32).contiguous()
+
+
+def _split_jitter(t_rand, n: int, num_samples: int):
+    """a render's ``t_rand`` argument as (KeyedJitter or None, contiguous float32 [n, num_samples] tensor or None)"""
+    if isinstance(t_rand, KeyedJitter):
+        return t_rand, None
+    if t_rand is not None:
+        _require_hip(t_rand, "t_rand")
+        t_rand = t_rand.detach().to(torch.float32).contiguous()
+        if tuple(t_rand.shape) != (n, num_samples):
+            raise ValueError(f"t_rand must be [{n}, {num_samples}], got {tuple(t_rand.shape)}")
+    return None, t_rand
+
+
+def _unpack_saved(saved, has_second: bool, has_rand, keyed):
+    """What the render ops save for backward -- first, [second], origins, directions, then per render its four caches and its
+    t_rand tensor if it had one -- as (first, second, origins, directions, [caches per render], [t_rand or KeyedJitter per render])"""
+    saved = list(saved)
+    first = saved.pop(0)
+    second = saved.pop(0) if has_second else None
+    origins, directions = saved.pop(0), saved.pop(0)
+    caches, t_rands = [], []
+    for rand, key in zip(has_rand, keyed):
+        caches.append(tuple(saved[:4]))
+        del saved[:4]
+        t_rands.append(saved.pop(0) if rand else key)
+    return first, second, origins, directions, caches, t_rands
+
+
+def _check_tensors_current(grid: VoxelGrid, first: Tensor, second: Optional[Tensor]) -> None:
+    cur_first, cur_second = grid.kernel_tensors()
+    if cur_first.data_ptr() != first.data_ptr() or (second is not None and cur_second.data_ptr() != second.data_ptr()):
+        raise RuntimeError("the VoxelGrid's tensors were replaced between forward and backward")
+
+
 class _ReluFieldRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, first, second, origins, directions, t_rand, grid: VoxelGrid, num_samples, near, far, flags, need_grad):
@@ -647,14 +669,7 @@ class _ReluFieldRender(torch.autograd.Function):
         origins = origins.detach().to(torch.float32).contiguous()
         directions = directions.detach().to(torch.float32).contiguous()
         n = origins.shape[0]
-        keyed = t_rand if isinstance(t_rand, KeyedJitter) else None
-        if keyed is not None:
-            t_rand = None
-        if t_rand is not None:
-            _require_hip(t_rand, "t_rand")
-            t_rand = t_rand.detach().to(torch.float32).contiguous()
-            if tuple(t_rand.shape) != (n, num_samples):
-                raise ValueError(f"t_rand must be [{n}, {num_samples}], got {tuple(t_rand.shape)}")
+        keyed, t_rand = _split_jitter(t_rand, n, num_samples)
         key_hist = None
         brick_size = _autograd_brick_size(grid)
         if need_grad and _autograd_uses_bricks(grid, int(flags), n, int(num_samples)):
@@ -690,20 +705,14 @@ class _ReluFieldRender(torch.autograd.Function):
             ret_d, ret_f = _ReluFieldRender._grid_backward(ctx, g_colour, g_depth, g_acc)
         g_o = g_dir = None
         if ctx.need_rays:
-            saved = list(ctx.saved_tensors)
-            origins, directions, cache, tcache, stop, cmask = saved[1 + ctx.has_second : 7 + ctx.has_second]
-            t_rand = saved[7 + ctx.has_second] if ctx.has_rand else ctx.keyed
-
-            def prep(g):
-                return None if g is None else g.detach().to(torch.float32).contiguous()
-
+            _, _, origins, directions, (caches,), (t_rand,) = _unpack_saved(ctx.saved_tensors, ctx.has_second, [ctx.has_rand], [ctx.keyed])
             want_o, want_d = bool(ctx.needs_input_grad[2]), bool(ctx.needs_input_grad[3])
             if g_colour is None and g_depth is None and g_acc is None:
                 g_o = torch.zeros_like(origins) if want_o else None
                 g_dir = torch.zeros_like(directions) if want_d else None
             else:
                 g_o, g_dir = render_backward_rays_raw(ctx.grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags,
-                                                      (cache, tcache, stop, cmask), prep(g_colour), prep(g_depth), prep(g_acc), want_o, want_d)
+                                                      caches, _prep_grad(g_colour), _prep_grad(g_depth), _prep_grad(g_acc), want_o, want_d)
             g_o = None if g_o is None else g_o.to(ctx.ray_dtypes[0])
             g_dir = None if g_dir is None else g_dir.to(ctx.ray_dtypes[1])
         return ret_d, ret_f, g_o, g_dir, None, None, None, None, None, None, None
@@ -711,18 +720,9 @@ class _ReluFieldRender(torch.autograd.Function):
     @staticmethod
     def _grid_backward(ctx, g_colour, g_depth, g_acc):
         """The adjoint into the grid tensors (atomic or binned), exactly as before ray gradients existed."""
-        saved = list(ctx.saved_tensors)
-        first = saved.pop(0)
-        second = saved.pop(0) if ctx.has_second else None
-        origins, directions, cache, tcache, stop, cmask = saved[:6]
-        t_rand = saved[6] if ctx.has_rand else ctx.keyed
+        first, second, origins, directions, (caches,), (t_rand,) = _unpack_saved(ctx.saved_tensors, ctx.has_second, [ctx.has_rand], [ctx.keyed])
         grid: VoxelGrid = ctx.grid
-        cur_first, cur_second = grid.kernel_tensors()
-        if cur_first.data_ptr() != first.data_ptr() or (second is not None and cur_second.data_ptr() != second.data_ptr()):
-            raise RuntimeError("the VoxelGrid's tensors were replaced between forward and backward")
-
-        def prep(g):
-            return None if g is None else g.detach().to(torch.float32).contiguous()
+        _check_tensors_current(grid, first, second)
 
         # gradient buffers: a caller-provided flat bucket when there is one (optim.FlatGrid), else fresh tensors
         bucket = getattr(grid, "_grad_bucket", None)
@@ -750,8 +750,8 @@ class _ReluFieldRender(torch.autograd.Function):
             records = torch.empty((origins.shape[0] * ctx.num_samples, expanded_record_floats(grid, diffuse)), dtype=torch.float32, device=dev)
             bin_offsets(hist, offsets, cursor)
             render_backward_emit_direct_raw(
-                grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags, (cache, tcache, stop, cmask),
-                prep(g_colour), prep(g_depth), prep(g_acc), ctx.brick_size, cursor, records, hist_clear=hist,
+                grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags, caches,
+                _prep_grad(g_colour), _prep_grad(g_depth), _prep_grad(g_acc), ctx.brick_size, cursor, records, hist_clear=hist,
             )
             _return_hist(hist)  # (zero again once the emit launch above has run: every later user is behind it on the stream)
             if bucket is not None and getattr(bucket, "deferred", False) and bucket.matches(first, second) and ctx.brick_size == bucket.brick_size:
@@ -768,8 +768,8 @@ class _ReluFieldRender(torch.autograd.Function):
                 raise RuntimeError("deferred gradients (optim.FlatGrid(deferred=True)): a render can be back-propagated once per optimizer step "
                                    "(its record counters were consumed by the first backward pass); use FlatGrid(deferred=False) for retained graphs")
             render_backward_raw(
-                grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags, (cache, tcache, stop, cmask),
-                prep(g_colour), prep(g_depth), prep(g_acc), gd, gf,
+                grid, origins, directions, t_rand, ctx.num_samples, ctx.near, ctx.far, ctx.flags, caches,
+                _prep_grad(g_colour), _prep_grad(g_depth), _prep_grad(g_acc), gd, gf,
             )
         return ret_d, ret_f
 
@@ -789,16 +789,7 @@ class _ReluFieldRenderPair(torch.autograd.Function):
         origins = origins.detach().to(torch.float32).contiguous()
         directions = directions.detach().to(torch.float32).contiguous()
         n, S = origins.shape[0], int(num_samples)
-        t_rands, keyed = [], []
-        for t in (t_rand0, t_rand1):
-            k = t if isinstance(t, KeyedJitter) else None
-            if k is None and t is not None:
-                _require_hip(t, "t_rand")
-                t = t.detach().to(torch.float32).contiguous()
-                if tuple(t.shape) != (n, S):
-                    raise ValueError(f"t_rand must be [{n}, {S}], got {tuple(t.shape)}")
-            keyed.append(k)
-            t_rands.append(None if k is not None else t)
+        keyed, t_rands = zip(*(_split_jitter(t, n, S) for t in (t_rand0, t_rand1)))
         brick_size = _autograd_brick_size(grid)
         nb = brick_counts(grid, brick_size)
         hists = [_take_hist(origins.device, nb[0] * nb[1] * nb[2] * 8) for _ in range(2)]
@@ -824,31 +815,17 @@ class _ReluFieldRenderPair(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gc0, gd0, ga0, _gq0, gc1, gd1, ga1, _gq1):
-        saved = list(ctx.saved_tensors)
-        first = saved.pop(0)
-        second = saved.pop(0) if ctx.has_second else None
-        origins, directions = saved.pop(0), saved.pop(0)
-        caches2, t_rands = [], []
-        for i in range(2):
-            caches2.append(tuple(saved[:4]))
-            del saved[:4]
-            t_rands.append(saved.pop(0) if ctx.has_rand[i] else ctx.keyed[i])
+        first, second, origins, directions, caches2, t_rands = _unpack_saved(ctx.saved_tensors, ctx.has_second, ctx.has_rand, ctx.keyed)
         grid: VoxelGrid = ctx.grid
         if ctx.hists is None:
             raise RuntimeError("a render pair can be back-propagated once (its record counters were consumed by the first backward pass)")
-        cur_first, cur_second = grid.kernel_tensors()
-        if cur_first.data_ptr() != first.data_ptr() or (second is not None and cur_second.data_ptr() != second.data_ptr()):
-            raise RuntimeError("the VoxelGrid's tensors were replaced between forward and backward")
-
-        def prep(g):
-            return None if g is None else g.detach().to(torch.float32).contiguous()
-
+        _check_tensors_current(grid, first, second)
         dev, n, S = origins.device, origins.shape[0], ctx.num_samples
         hists, nkeys = ctx.hists, int(ctx.hists[0].numel())
         offsets2 = torch.empty((2, nkeys + 1), dtype=torch.int64, device=dev)
         cursor2 = torch.empty((2, nkeys), dtype=torch.int32, device=dev)
         records2 = [torch.empty((n * S, expanded_record_floats(grid, bool(i))), dtype=torch.float32, device=dev) for i in range(2)]
-        g_colours, g_depths, g_accs = [prep(gc0), prep(gc1)], [prep(gd0), prep(gd1)], [prep(ga0), prep(ga1)]
+        g_colours, g_depths, g_accs = [_prep_grad(gc0), _prep_grad(gc1)], [_prep_grad(gd0), _prep_grad(gd1)], [_prep_grad(ga0), _prep_grad(ga1)]
         colours_only = all(g is not None for g in g_colours) and all(g is None for g in g_depths + g_accs)
         paired = colours_only and render_backward_emit_direct_pair_raw(grid, origins, directions, t_rands, S, ctx.near, ctx.far, ctx.flags, caches2, g_colours,
                                                                        ctx.brick_size, hists, offsets2, cursor2, records2)
