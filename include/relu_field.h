@@ -409,6 +409,24 @@ int rf_upsample_grid(const RFGrid* src, const RFGrid* dst, void* stream);
  * Parameters (thre3d_reprs/voxels.py:70-71) can keep an RF_LAYOUT_SPLIT shadow of them for the forward passes this way. */
 int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream);
 
+/* Total-variation regulariser of the grid parameters (Plenoxels / DVGO / TensoRF ship the same term): for node n, channel c and
+ * axis a, d_a = theta[n + e_a] - theta[n] (0 where n + e_a is outside the grid), r = sqrt(epsilon + sum_a d_a^2),
+ *   TV_density = mean over nodes of r(density),  TV_features = mean over nodes and the F feature channels of r.
+ * The density is the RAW parameter (before density_scale and the activation: independent of density_mode).  The call ADDS
+ *   weight_density * d TV_density / d theta   and   weight_features * d TV_features / d theta
+ * to grad_first_dev / grad_second_dev, which follow the layout of `grid` like every gradient buffer of this ABI (split / bricked:
+ * the base record holds the density and the three degree-0 coefficients; padding nodes of bricked storage are neither read nor
+ * written).  One thread owns an element and gathers its six terms: no atomics on the gradient, bitwise reproducible.  A channel whose
+ * weight is 0 is left bit-untouched, and the tensor it alone lives in may be NULL (grad_second_dev is NULL anyway for F == 3 on split /
+ * bricked storage).  sums_dev (optional, 2 floats, the caller zeroes them): sums_dev[0] += sum of r(density), sums_dev[1] += sum of
+ * r(features), UNWEIGHTED -- the caller divides by N and N * F for the two TV values (the convention of rf_l1_loss_grad).
+ * Both weights 0: nothing is launched (sums included), RF_OK.  Before any device access: RF_ERR_NULL_POINTER (grid, its tensors, a
+ * gradient tensor a non-zero weight needs), RF_ERR_BAD_SHAPE (dims, a non-finite or non-positive epsilon, a negative or non-finite
+ * weight, a gradient pointer that IS the parameter tensor it belongs to).  Every F in {3, 12, 27, 48}, every density mode, dims >= 1.
+ * (Added to ABI version 4 compatibly: no existing struct or signature changed.) */
+int rf_tv_grad(const RFGrid* grid, float weight_density, float weight_features, float epsilon, float* grad_first_dev,
+               float* grad_second_dev, float* sums_dev, void* stream);
+
 /* Iso-surface extraction (csrc/mesh_kernels.hip; the contract -- field, lattice, Kuhn tetrahedra, edge keys, orientation and
  * canonical order -- is in that file's header and in DESIGN.md).  The level set sigma = iso_level of the grid's density on the
  * lattice of `subdivisions` (1..8) points per voxel and axis plus one guard plane on each AABB face, as a closed oriented mesh.

@@ -91,6 +91,9 @@ def synthetic_dataset(dev, size, n_views, samples):
 @click.option("--synthetic_size", type=click.INT, required=False, default=200, help="image size of the synthetic scene")
 @click.option("--global_batch", type=click.BOOL, required=False, default=False,
               help="data parallel: --ray_batch_size is the GLOBAL batch split over the ranks (N GPUs reproduce the single-GPU run); default: per rank")
+@click.option("--tv_density_weight", type=click.FLOAT, required=False, default=0.0, help="weight of the total variation of the raw densities (0: off)")
+@click.option("--tv_feature_weight", type=click.FLOAT, required=False, default=0.0, help="weight of the total variation of the SH features (0: off)")
+@click.option("--tv_epsilon", type=click.FLOAT, required=False, default=1e-8, help="epsilon inside the square root of the total variation")
 @click.option("--seed", type=click.INT, required=False, default=42, help="seed of torch's generators")
 # fmt: on
 # -------------------------------------------------------------------------------------
@@ -140,7 +143,8 @@ def main(**kwargs) -> None:
         lr_decay_gamma_per_stage=config["lr_decay_gamma_per_stage"], lr_decay_steps_per_stage=config["lr_decay_steps_per_stage"],
         stagewise_lr_decay_gamma=config["stagewise_lr_decay_gamma"], save_freq=config["save_frequency"], test_freq=config["test_frequency"],
         summary_freq=config["summary_frequency"], apply_diffuse_render_regularization=config["apply_diffuse_render_regularization"],
-        global_batch=config["global_batch"],
+        global_batch=config["global_batch"], tv_density_weight=config["tv_density_weight"], tv_feature_weight=config["tv_feature_weight"],
+        tv_epsilon=config["tv_epsilon"],
     )
 
 

@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = [
     "rf_build_occupancy",
     "rf_upsample_grid",
     "rf_convert_grid",
+    "rf_tv_grad",
     "rf_l1_loss_grad",
     "rf_adam_step",
     "rf_train_step",
@@ -307,6 +308,7 @@ def load() -> C.CDLL:
     lib.rf_render_backward_rays.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, C.POINTER(RFRenderOut), C.POINTER(RFRenderGrads), vp, vp, vp]
     lib.rf_upsample_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), vp]
     lib.rf_convert_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), vp]
+    lib.rf_tv_grad.argtypes = [C.POINTER(RFGrid), f32, f32, f32, vp, vp, vp, vp]
     lib.rf_build_occupancy.argtypes = [C.POINTER(RFGrid), f32, vp, vp]
     lib.rf_l1_loss_grad.argtypes = [vp, vp, i64, f32, vp, vp, vp]
     lib.rf_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, vp]

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
@@ -4351,6 +4352,147 @@ __global__ __launch_bounds__(1024) void loss_and_offsets_kernel(L1Sets sets, con
   }
 }
 
+// =============================================================================================
+// rf_tv_grad: total variation of the raw grid parameters.  For node n and channel c, with
+// d_a(n) = theta[n + e_a] - theta[n] (0 where n + e_a lies outside the grid) and r(n) = sqrt(eps + sum_a d_a(n)^2):
+//   g(n) = w * [ -(d_x(n) + d_y(n) + d_z(n)) / r(n) + sum_a d_a(n - e_a) / r(n - e_a) ]      (terms outside the grid dropped)
+// GATHER form: one thread owns V consecutive channels of one (y, z) column of an x-slab of kTvSlab nodes, reads the parameters
+// only, and adds g to its own gradient elements -- no atomics on the gradient, bitwise reproducible.  Lanes run over the
+// (z, channel) row, so every neighbour load of a wave is a contiguous row segment (split storage, SH degree 0 / 2: one float4 of a
+// node per lane).  Walking x in registers, the centre, its -y and its -z neighbour are the +x loads of the plane before and the
+// x term d_x(n - e_x) / r(n - e_x) is the plane before's own d_x / r: 7 parameter loads per element instead of 13, the rest
+// served by L1 / L2 (the four waves of a workgroup are four neighbouring y rows).  Padding nodes of bricked storage are never
+// addressed: every neighbour is tested against the grid's dims first.
+// =============================================================================================
+constexpr int kTvSlab = 8;   // x planes per workgroup
+constexpr int kTvRows = 4;   // y rows per workgroup (one wave each)
+
+template <int V>
+struct TvVec {
+  float v[V];
+};
+template <int V>
+__device__ __forceinline__ TvVec<V> tv_load(const float* p) {
+  TvVec<V> r;
+  if constexpr (V == 4) {
+    const float4 q = *reinterpret_cast<const float4*>(p);
+    r.v[0] = q.x, r.v[1] = q.y, r.v[2] = q.z, r.v[3] = q.w;
+  } else {
+    r.v[0] = *p;
+  }
+  return r;
+}
+template <int V>
+__device__ __forceinline__ void tv_store(float* p, const TvVec<V>& r) {
+  if constexpr (V == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+  } else {
+    *p = r.v[0];
+  }
+}
+// 1 / r = 1 / sqrt(eps + dx^2 + dy^2 + dz^2): three fused multiply-adds, a correctly rounded square root and division
+__device__ __forceinline__ float tv_inv_norm(float dx, float dy, float dz, float eps) {
+  return 1.0f / sqrtf(fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps))));
+}
+
+template <int K, int V, bool SUMS>
+__global__ __launch_bounds__(kWave * kTvRows) void tv_grad_kernel(GridArgs g, float wd, float wf, float eps, float* __restrict__ gfirst,
+                                                                  float* __restrict__ gsecond, float* __restrict__ sums) {
+  constexpr int C = 3 * K + 1, Q = C / V;  // channels per node in accumulator order (channel_offset), lanes per node
+  const unsigned it = blockIdx.x * kWave + threadIdx.x;
+  const int z = (int)(it / Q), ch = (int)(it - (unsigned)z * Q) * V;
+  const int y = blockIdx.y * kTvRows + threadIdx.y;
+  const int x0 = blockIdx.z * kTvSlab, x1 = min(x0 + kTvSlab, g.X);
+  float sum_d = 0.0f, sum_f = 0.0f;
+  float w[V];
+  bool write = false;
+#pragma unroll
+  for (int c = 0; c < V; ++c) {
+    w[c] = (ch + c == 0) ? wd : wf;
+    write = write || w[c] != 0.0f;
+  }
+  if (y < g.Y && z < g.Z && (write || SUMS)) {
+    bool first;
+    const long long coff = channel_offset(g, 0u, ch, K, first);  // the channel's place inside a node's record
+    const float* src = (first ? g.dens : g.feat) + coff;
+    float* dst = (first ? gfirst : gsecond) + coff;
+    const long long stride = first ? g.dstride : g.fstride;
+    auto off = [&](int xi, int yi, int zi) { return (long long)node_lin(g, xi, yi, zi) * stride; };
+    auto at = [&](int xi, int yi, int zi) { return tv_load<V>(src + off(xi, yi, zi)); };
+    const bool ly = y > 0, lz = z > 0, hy = y + 1 < g.Y, hz = z + 1 < g.Z;
+    TvVec<V> t = at(x0, y, z), my = t, mz = t, tx;
+    if (ly) my = at(x0, y - 1, z);
+    if (lz) mz = at(x0, y, z - 1);
+    if (x0 > 0) {  // the x term of the slab's first plane, computed the way the loop computes it for the plane before
+      const TvVec<V> m = at(x0 - 1, y, z), py = hy ? at(x0 - 1, y + 1, z) : m, pz = hz ? at(x0 - 1, y, z + 1) : m;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float dx = t.v[c] - m.v[c];
+        tx.v[c] = dx * tv_inv_norm(dx, py.v[c] - m.v[c], pz.v[c] - m.v[c], eps);
+      }
+    }
+    for (int x = x0; x < x1; ++x) {
+      const bool hx = x + 1 < g.X;
+      // a missing upper neighbour is replaced by the node itself: its difference is then exactly 0
+      const TvVec<V> fx = hx ? at(x + 1, y, z) : t, fy = hy ? at(x, y + 1, z) : t, fz = hz ? at(x, y, z + 1) : t;
+      TvVec<V> myx = my, myz = my, mzx = mz, mzy = mz;
+      if (ly) {
+        if (hx) myx = at(x + 1, y - 1, z);
+        if (hz) myz = at(x, y - 1, z + 1);
+      }
+      if (lz) {
+        if (hx) mzx = at(x + 1, y, z - 1);
+        if (hy) mzy = at(x, y + 1, z - 1);
+      }
+      TvVec<V> acc;
+#pragma unroll
+      for (int c = 0; c < V; ++c) {
+        const float dx = fx.v[c] - t.v[c], dy = fy.v[c] - t.v[c], dz = fz.v[c] - t.v[c];
+        const float inv = tv_inv_norm(dx, dy, dz, eps);
+        const float px = dx * inv;
+        float a = (-px - dy * inv) - dz * inv;
+        if (x > 0) a += tx.v[c];
+        if (ly) {
+          const float e = t.v[c] - my.v[c];
+          a += e * tv_inv_norm(myx.v[c] - my.v[c], e, myz.v[c] - my.v[c], eps);
+        }
+        if (lz) {
+          const float e = t.v[c] - mz.v[c];
+          a += e * tv_inv_norm(mzx.v[c] - mz.v[c], mzy.v[c] - mz.v[c], e, eps);
+        }
+        tx.v[c] = px;
+        acc.v[c] = a;
+        if (SUMS) {
+          const float r = sqrtf(fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps))));
+          if (ch + c == 0) sum_d += r; else sum_f += r;
+        }
+      }
+      if (write) {  // (a channel whose weight is 0 keeps its bits; a tensor whose channels all have weight 0 is not touched)
+        float* p = dst + off(x, y, z);
+        TvVec<V> old = tv_load<V>(p);
+#pragma unroll
+        for (int c = 0; c < V; ++c)
+          if (w[c] != 0.0f) old.v[c] += w[c] * acc.v[c];
+        tv_store<V>(p, old);
+      }
+      t = fx, my = myx, mz = mzx;
+    }
+  }
+  if (SUMS) {  // sum of r per kind: wave -> workgroup -> one atomic add each (the sums are for logging; the gradient has no atomics)
+    __shared__ float s_part[2][kTvRows];
+    sum_d = wave_sum(sum_d);
+    sum_f = wave_sum(sum_f);
+    if (threadIdx.x == 0) s_part[0][threadIdx.y] = sum_d, s_part[1][threadIdx.y] = sum_f;
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+      float a = 0.0f, b = 0.0f;
+      for (int r = 0; r < kTvRows; ++r) a += s_part[0][r], b += s_part[1][r];
+      unsafeAtomicAdd(sums + 0, a);
+      unsafeAtomicAdd(sums + 1, b);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ---------------------------------------------------------------------------------------------
@@ -5344,6 +5486,46 @@ int rf_upsample_grid(const RFGrid* src, const RFGrid* dst, void* stream) {
   hipLaunchKernelGGL(upsample_grid_kernel, dim3(grid_1d(total, 256, 256LL * 64)), dim3(256), 0, (hipStream_t)stream, gs, gd,
                      const_cast<float*>(dst->densities_dev), const_cast<float*>(dst->features_dev), total);
   return launch_status();
+}
+
+int rf_tv_grad(const RFGrid* grid, float weight_density, float weight_features, float epsilon, float* grad_first_dev,
+               float* grad_second_dev, float* sums_dev, void* stream) {
+  const int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return RF_ERR_BAD_SHAPE;
+  if (!(weight_density >= 0.0f) || !(weight_features >= 0.0f) || !std::isfinite(weight_density) || !std::isfinite(weight_features)) return RF_ERR_BAD_SHAPE;
+  if (weight_density == 0.0f && weight_features == 0.0f) return RF_OK;
+  // which gradient tensors the weights reach: split / bricked storage keeps the degree-0 coefficients beside the density
+  const bool split = grid->layout != RF_LAYOUT_REFERENCE;
+  const bool need_first = weight_density != 0.0f || split;
+  const bool need_second = weight_features != 0.0f && !(split && grid->num_features == 3);
+  if ((need_first && !grad_first_dev) || (need_second && !grad_second_dev)) return RF_ERR_NULL_POINTER;
+  // the gradient is added to tensors of its own, never to the parameters
+  if ((grad_first_dev && grad_first_dev == grid->densities_dev) || (grad_second_dev && grad_second_dev == grid->features_dev)) return RF_ERR_BAD_SHAPE;
+  const GridArgs g = to_args(grid);
+  const int K = g.F / 3, C = g.F + 1;
+  // one float4 of a node per lane where every node record is whole, aligned float4s
+  const uintptr_t ptrs = (uintptr_t)grid->densities_dev | (uintptr_t)grid->features_dev | (uintptr_t)grad_first_dev | (uintptr_t)grad_second_dev;
+  const bool quads = split && C % 4 == 0 && g.dstride % 4 == 0 && g.fstride % 4 == 0 && (ptrs & 15u) == 0;
+  const long long row = (long long)g.Z * (quads ? C / 4 : C);
+  const dim3 blocks((unsigned)((row + kWave - 1) / kWave), (unsigned)((g.Y + kTvRows - 1) / kTvRows), (unsigned)((g.X + kTvSlab - 1) / kTvSlab));
+  const dim3 threads(kWave, kTvRows);
+  // the weights of the two MEANS as per-element factors: w = lambda_D / N, lambda_F / (N F)
+  const double nodes = (double)g.X * g.Y * g.Z;
+  const float wd = (float)((double)weight_density / nodes), wf = (float)((double)weight_features / (nodes * g.F));
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, blocks, threads, 0, (hipStream_t)stream, g, wd, wf, epsilon, grad_first_dev, grad_second_dev, sums_dev);
+    return launch_status();
+  };
+  if (quads)
+    return dispatch_sh(K, ShEven{}, [&](auto k) {
+      constexpr int KK = decltype(k)::value;
+      return sums_dev ? launch(tv_grad_kernel<KK, 4, true>) : launch(tv_grad_kernel<KK, 4, false>);
+    });
+  return dispatch_sh(K, ShAll{}, [&](auto k) {
+    constexpr int KK = decltype(k)::value;
+    return sums_dev ? launch(tv_grad_kernel<KK, 1, true>) : launch(tv_grad_kernel<KK, 1, false>);
+  });
 }
 
 int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream) {

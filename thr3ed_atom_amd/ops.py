@@ -972,6 +972,87 @@ def grid_query(grid: VoxelGrid, points: Tensor) -> Tensor:
     return _GridQuery.apply(first, second, points, grid)
 
 
+def tv_grad_raw(grid: VoxelGrid, weight_density: float, weight_features: float, grad_first: Optional[Tensor], grad_second: Optional[Tensor],
+                sums: Optional[Tensor] = None, epsilon: float = 1e-8) -> None:
+    """Enqueue rf_tv_grad: ADD ``weight_density * d TV_density + weight_features * d TV_features`` (the total variation of the raw
+    grid parameters, include/relu_field.h) to ``grad_first`` / ``grad_second`` -- tensors in the layout of ``grid.kernel_tensors()``;
+    one may be None when no non-zero weight reaches it.  ``sums`` [2] (optional, zeroed by the caller): += (sum of r over the
+    densities, sum of r over the features), unweighted -- TV_density = sums[0] / N, TV_features = sums[1] / (N F)."""
+    lib = _lib.load()
+    first, _ = grid.kernel_tensors()
+    _require_hip(first, "grid tensor")
+    for t in (grad_first, grad_second, sums):
+        if t is not None:
+            _require_hip(t, "gradient / sums tensor")
+            if not (t.is_contiguous() and t.dtype == torch.float32):
+                raise ValueError("rf_tv_grad takes contiguous float32 tensors")
+    first_shape, second_shape = (tuple(t.shape) if t is not None else None for t in grid.kernel_tensors())
+    if (grad_first is not None and tuple(grad_first.shape) != first_shape) or (grad_second is not None and tuple(grad_second.shape) != second_shape):
+        raise ValueError("the gradient tensors must have the shapes of grid.kernel_tensors()")
+    if sums is not None and sums.numel() < 2:
+        raise ValueError("sums must hold two floats")
+    rf_grid = grid.to_rf_grid()
+    with _span("tv_grad", first.device):
+        rc = lib.rf_tv_grad(C.byref(rf_grid), float(weight_density), float(weight_features), float(epsilon), _ptr(grad_first), _ptr(grad_second),
+                            _ptr(sums), _stream(first.device))
+    _lib.check(rc, "rf_tv_grad")
+
+
+class _TotalVariation(torch.autograd.Function):
+    """(TV_density, TV_features) of a grid.  Forward: one launch of rf_tv_grad for its two sums (the kernel has no sums-only mode:
+    the gradient it also writes goes to scratch tensors that are dropped at once -- nothing grid-sized is kept for backward).
+    Backward: one launch with the two upstream scalars as weights, into the grid's gradient bucket when it has one."""
+
+    @staticmethod
+    def forward(ctx, first, second, grid: VoxelGrid, epsilon):
+        _require_hip(first, "grid tensor")
+        sums = torch.zeros(2, dtype=torch.float32, device=first.device)
+        tv_grad_raw(grid, 1.0, 1.0, torch.zeros_like(first), None if second is None else torch.zeros_like(second), sums, epsilon)
+        nodes = float(np.prod(grid.grid_dims))
+        ctx.grid, ctx.epsilon, ctx.has_second = grid, float(epsilon), second is not None
+        ctx.save_for_backward(*([first] + ([second] if second is not None else [])))
+        ctx.set_materialize_grads(False)
+        return sums[0] / nodes, sums[1] / (nodes * grid.num_features)
+
+    @staticmethod
+    def backward(ctx, g_density, g_features):
+        saved = list(ctx.saved_tensors)
+        first, second = saved[0], (saved[1] if ctx.has_second else None)
+        grid: VoxelGrid = ctx.grid
+        _check_tensors_current(grid, first, second)
+        # the weights cross the C ABI by value: reading the two upstream scalars is one host synchronisation
+        wd = 0.0 if g_density is None else float(g_density)
+        wf = 0.0 if g_features is None else float(g_features)
+        if wd < 0.0 or wf < 0.0:
+            raise ValueError("total_variation is a regulariser: it takes non-negative upstream gradients (loss weights)")
+        bucket = getattr(grid, "_grad_bucket", None)
+        if bucket is not None and bucket.matches(first, second):
+            if getattr(bucket, "deferred", False):
+                raise RuntimeError("deferred gradients (optim.FlatGrid(deferred=True)) carry record lists only: total_variation needs FlatGrid(deferred=False)")
+            gd, gf = bucket.views_for_accumulation()
+            ret_d, ret_f = bucket.autograd_return()
+        else:
+            gd = torch.zeros_like(first)
+            gf = None if second is None else torch.zeros_like(second)
+            ret_d, ret_f = gd, gf
+        tv_grad_raw(grid, wd, wf, gd, gf, None, ctx.epsilon)
+        return ret_d, ret_f, None, None
+
+
+def total_variation(grid: VoxelGrid, epsilon: float = 1e-8) -> Tuple[Tensor, Tensor]:
+    """Total variation of the grid's raw parameters as two differentiable 0-d tensors:
+
+        d_a(n, c) = theta[n + e_a, c] - theta[n, c]  (0 at the upper faces),   r = sqrt(epsilon + sum_a d_a^2)
+        tv_density = mean_n r(n, density),   tv_features = mean_{n, c} r(n, c) over the F feature channels
+
+    on every storage ("reference", "split", "bricked"); the density is the raw parameter, before ``expected_density_scale`` and the
+    activation.  ``loss = render_loss + 1e-3 * tv_density + 1e-4 * tv_features`` back-propagates one HIP launch (rf_tv_grad) that adds
+    into the grid's gradient bucket (optim.FlatGrid) when it has one and returns gradient tensors in the parameters' layout otherwise.
+    The weights must be non-negative."""
+    first, second = grid.kernel_tensors()
+    return _TotalVariation.apply(first, second, grid, float(epsilon))
+
+
 def render_flags(white_bkgd: bool, render_diffuse: bool, optimized_sampling: bool, use_occupancy: bool) -> int:
     flags = 0
     flags |= _lib.FLAG_WHITE_BKGD if white_bkgd else 0

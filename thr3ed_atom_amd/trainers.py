@@ -130,13 +130,17 @@ class StepStats:
     when a value is READ: an iteration enqueues no extra launch for numbers that are looked at every ``summary_freq`` steps.  The ring
     slot is re-used LOSS_RING iterations later: a StepStats read after that RAISES instead of returning another iteration's sums
     (``ring`` = (the executor's step counter, the step that produced this object)); ``materialize()`` copies the four sums out of
-    the ring (one small launch) for code that keeps a history of StepStats objects."""
+    the ring (one small launch) for code that keeps a history of StepStats objects.
+    ``tv_density`` / ``tv_features``: the total-variation values of the grid the step's regulariser saw (TrainStepper(tv_*_weight=...)),
+    read the same lazy way from the two sums rf_tv_grad wrote (``tv`` = (sums [2] in a ring slot, nodes N, features F, ring)); None
+    when TV is off."""
 
     def __init__(self, specular_loss=None, diffuse_loss=None, specular_mse=None, diffuse_mse=None, sums: Optional[Tensor] = None, count: float = 1.0,
-                 has_diffuse: bool = True, ring=None):
+                 has_diffuse: bool = True, ring=None, tv=None):
         self._values = (specular_loss, diffuse_loss, specular_mse, diffuse_mse)
         self._sums, self._count, self._has_diffuse = sums, float(count), has_diffuse
         self._ring = ring  # (executor dict holding "serial", serial of the producing step) or None
+        self._tv = tv
 
     def _live_sums(self) -> Tensor:
         if self._ring is not None:
@@ -151,7 +155,24 @@ class StepStats:
         if self._sums is not None and self._ring is not None:
             self._sums = self._live_sums().clone()
             self._ring = None
+        if self._tv is not None and self._tv[3] is not None:
+            self._tv = (self._live_tv().clone(),) + self._tv[1:3] + (None,)
         return self
+
+    def _live_tv(self) -> Tensor:
+        sums, _, _, ring = self._tv
+        if ring is not None and ring[0]["serial"] - ring[1] >= LOSS_RING:
+            raise RuntimeError(f"this StepStats was produced {ring[0]['serial'] - ring[1]} iterations ago: its slot of the TV ring ({LOSS_RING} iterations) "
+                               "has been re-used -- read it earlier or keep StepStats.materialize() of it")
+        return sums
+
+    @property
+    def tv_density(self):
+        return None if self._tv is None else self._live_tv()[0] / self._tv[1]
+
+    @property
+    def tv_features(self):
+        return None if self._tv is None else self._live_tv()[1] / (self._tv[1] * self._tv[2])
 
     def _get(self, i: int, j: int):
         if self._sums is None:
@@ -238,8 +259,19 @@ class TrainStepper:
         fuse_optimizer: Optional[bool] = None,
         exchange: str = "auto",
         brick_size: Optional[int] = None,
+        tv_density_weight: float = 0.0,
+        tv_feature_weight: float = 0.0,
+        tv_epsilon: float = 1e-8,
     ):
-        """``brick_size``: 8 or 4 (cubic bricks of the binned backward) or ops.BRICK_4X8X8; None = $RF_BRICK_SIZE, else 4 x 8 x 8 for the
+        """``tv_density_weight`` / ``tv_feature_weight`` (lambda_D, lambda_F >= 0): total-variation regularisation of the raw grid
+        parameters, ``loss += lambda_D * TV_density + lambda_F * TV_features`` (ops.total_variation; ``tv_epsilon`` inside the square
+        root).  One launch of rf_tv_grad per iteration adds its gradient to the gradient bucket after the render gradients and before
+        the data-parallel exchange and Adam -- so a step with TV keeps the bucket: ``fuse_optimizer`` resolves to False, the FlatGrid is
+        not deferred and ``exchange`` resolves to "dense" (an explicit fuse_optimizer=True or exchange="owner" raises).  Not scaled by
+        the data-parallel loss scale: every rank adds the whole TV gradient, whose mean over the ranks is the TV gradient.  With both
+        weights 0 (default) nothing changes: nothing is allocated or launched and every option resolves as without these arguments.
+
+        ``brick_size``: 8 or 4 (cubic bricks of the binned backward) or ops.BRICK_4X8X8; None = $RF_BRICK_SIZE, else 4 x 8 x 8 for the
         single-process step with Adam in the brick flush and 8 otherwise.
 
         ``ray_selection``: "randperm" draws torch.randperm over all B*H*W pixels exactly like the reference
@@ -252,6 +284,21 @@ class TrainStepper:
         across the block, where the reference re-draws independently per iteration)."""
         if ray_selection not in ("keyed", "randperm", "randperm_blocks"):
             raise ValueError("ray_selection must be 'keyed', 'randperm' or 'randperm_blocks'")
+        self.tv_density_weight, self.tv_feature_weight, self.tv_epsilon = float(tv_density_weight), float(tv_feature_weight), float(tv_epsilon)
+        for w in (self.tv_density_weight, self.tv_feature_weight):
+            if not (np.isfinite(w) and w >= 0.0):
+                raise ValueError("tv_density_weight and tv_feature_weight must be finite and non-negative")
+        self.tv = self.tv_density_weight > 0.0 or self.tv_feature_weight > 0.0
+        if self.tv and not (np.isfinite(self.tv_epsilon) and self.tv_epsilon > 0.0):
+            raise ValueError("tv_epsilon must be finite and positive")
+        # the TV gradient is ADDED to a gradient tensor in HBM before Adam reads it: the paths that never hold one cannot take it
+        if self.tv and fuse_optimizer:
+            raise ValueError("fuse_optimizer=True applies Adam inside the brick flush, where no gradient tensor exists in memory for the total-variation "
+                             "gradient to be added to: a step with a TV weight needs fuse_optimizer=False (the default with TV)")
+        if self.tv and exchange == "owner":
+            raise ValueError("exchange='owner' exchanges gradient records and applies Adam inside the owners' brick flush, where no gradient tensor exists "
+                             "for the total-variation gradient to be added to: a step with a TV weight needs exchange='dense' (the default with TV)")
+        self._tv_ring = None
         self.ray_selection = ray_selection
         # fused=True runs the iteration as a fixed sequence of launches (forward, loss+gradient, backward per
         # render, then Adam which also clears the gradient bucket) without building an autograd graph;
@@ -291,7 +338,7 @@ class TrainStepper:
         self.data_parallel = data_parallel
         # autograd steps (fused=False) on a grid in the reference's own tensors: the backward passes leave record lists and the
         # optimizer sums them in one merged brick pass with Adam in its flush (optim.FlatGrid(deferred=True))
-        self.flat = FlatGrid(grid, deferred=not self.fused and not (self.data_parallel and rfdist._collectives_on()))
+        self.flat = FlatGrid(grid, deferred=not self.fused and not (self.data_parallel and rfdist._collectives_on()) and not self.tv)
         self.optimizer = FusedAdam(self.flat, lr=learning_rate, betas=(0.9, 0.999))
         if backward == "auto":
             # binned from 256 bricks of 8^3 nodes on: the brick pass has one workgroup per brick, and on the first grids of a progressive
@@ -321,7 +368,7 @@ class TrainStepper:
         for d in grid.grid_dims:
             padded_nodes *= (d + 7) // 8 * 8
         fits_flush = padded_nodes * max(4, grid.num_features - 3) < (1 << 31)
-        can_fuse = self.merged_bricks and single and grid.storage != "reference" and (grid.num_features + 1) % 4 == 0 and fits_flush
+        can_fuse = self.merged_bricks and single and grid.storage != "reference" and (grid.num_features + 1) % 4 == 0 and fits_flush and not self.tv
         # exchange (data parallel; the reference has none: modules/trainers.py:338-341 is one device's backward + step):
         #   "owner": OWNER-COMPUTES.  Every rank owns an equal range of x-slabs of bricks.  The ranks exchange their gradient RECORDS
         #     (48 / 32 B each, already sorted by brick, so what an owner needs of a rank's list is ONE slice) instead of the dense
@@ -332,7 +379,7 @@ class TrainStepper:
         if exchange not in ("auto", "owner", "dense"):
             raise ValueError("exchange must be 'auto', 'owner' or 'dense'")
         world = rfdist.world_size()
-        can_owner = (not single and can_merge and merge_bricks is not False and fuse_optimizer is not False and grid.storage != "reference"
+        can_owner = (not self.tv and not single and can_merge and merge_bricks is not False and fuse_optimizer is not False and grid.storage != "reference"
                      and (grid.num_features + 1) % 4 == 0 and fits_flush and world <= (8 if grid.num_features > 3 else 4) and self.brick_size == 8
                      and grid.grid_dims[0] % (8 * world) == 0)  # (a degree-0 grid's 2 W lists are all of ONE kind: at most 8 per brick pass)
         if exchange == "owner" and not can_owner:
@@ -443,13 +490,33 @@ class TrainStepper:
                 total = total + dl
                 diff_loss = dl.detach()
         total.backward(self._unit_gradient(total))
+        tv = self._add_tv_gradient()
         if self.data_parallel:
             rfdist.all_reduce_mean_(self.flat.flat_grad)
         self.optimizer.step()
         if not self.flat.deferred:  # (the deferred step re-laid the Parameters out and marked shadow and mask state itself)
             grid.invalidate_occupancy()
         self._grad_clean = False
-        return StepStats(spec_loss, diff_loss, spec_mse, diff_mse)
+        return StepStats(spec_loss, diff_loss, spec_mse, diff_mse, tv=tv)
+
+    def _add_tv_gradient(self):
+        """Total variation on: ONE launch of rf_tv_grad adds lambda_D dTV_density + lambda_F dTV_features to the gradient bucket -- after
+        the render gradients of the iteration are in it, before the data-parallel exchange and Adam -- and leaves the two sums of the
+        iteration in the next slot of a ring (StepStats reads them lazily).  Returns StepStats' ``tv`` argument; None when TV is off."""
+        if not self.tv:
+            return None
+        grid = self.vol_mod.thre3d_repr
+        gd, gf = self.flat.views_for_accumulation()
+        ring = self._tv_ring
+        if ring is None or ring["sums"].device != gd.device:
+            ring = self._tv_ring = {"sums": torch.zeros((LOSS_RING, 2), dtype=torch.float32, device=gd.device), "slot": 0, "serial": 0}
+        elif ring["slot"] == 0:
+            ring["sums"].zero_()  # a new turn of the ring (the kernel adds to its slot)
+        slot, ring["slot"] = ring["slot"], (ring["slot"] + 1) % LOSS_RING
+        ring["serial"] += 1
+        sums = ring["sums"][slot]
+        ops.tv_grad_raw(grid, self.tv_density_weight, self.tv_feature_weight, gd, gf, sums, self.tv_epsilon)
+        return (sums, float(np.prod(grid.grid_dims)), float(grid.num_features), (ring, ring["serial"]))
 
     def _draw_jitter(self, cfg, n: int, S: int, device, given, i: int, first_ray: int = 0):
         if given is not None:
@@ -546,14 +613,16 @@ class TrainStepper:
             rc = _lib.load().rf_train_step(C.byref(rf_grid), C.byref(st), torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(rc, "rf_train_step")
         del keep, jit
+        tv = None
         if self.fuse_optimizer:
             self._grad_clean = True  # the bucket is not used at all
         else:
+            tv = self._add_tv_gradient()
             if self.data_parallel and rfdist._collectives_on():
                 rfdist.all_reduce_mean_(self.flat.flat_grad)
             opt.step()
             self._grad_clean = False
-        return StepStats(sums=sums, count=3 * n, ring=(ex, serial))
+        return StepStats(sums=sums, count=3 * n, ring=(ex, serial), tv=tv)
 
     def _owner_state(self, ex, device):
         """Persistent state of the owner-computes exchange: who owns which x-slabs of bricks, the ranks' offset tables, where every
@@ -852,6 +921,7 @@ class TrainStepper:
                                             b["cursor"], b["sorted"], hist_clear=b["hist"])
             lists.append((b["sorted"], offsets, diffuse))
         opt = self.optimizer
+        tv = None
         if self.fuse_optimizer:
             opt.step_count += 1
             nd = self.flat.flat_gradient_parts()[0].numel()
@@ -863,12 +933,13 @@ class TrainStepper:
         else:
             gd, gf = self.flat.views_for_accumulation()
             brick_accumulate_raw(grid, self.brick_size, lists, gd, gf, accumulate=False)  # overwrites the whole bucket
+            tv = self._add_tv_gradient()
             if self.data_parallel and rfdist._collectives_on():
                 rfdist.all_reduce_mean_(self.flat.flat_grad)
             opt.step()
             self._grad_clean = False
         means = sums / float(3 * n)
-        return StepStats(means[0], means[2], means[1], means[3])
+        return StepStats(means[0], means[2], means[1], means[3], tv=tv)
 
     def _fused_step_on(self, rays: Rays, pixels: Tensor, t_rand_given=None) -> StepStats:
         vol_mod, grid = self.vol_mod, self.vol_mod.thre3d_repr
@@ -889,7 +960,8 @@ class TrainStepper:
         # data parallel: with split storage the diffuse pass only touches `base`, so the all-reduce of the `rest`
         # gradients (201 of the 235 MB at degree 2) starts right after the specular backward and overlaps it
         dp = self.data_parallel and rfdist._collectives_on()
-        overlap = dp and self.diffuse and grid.storage != "reference" and gf is not None
+        # (with total variation the exchange waits for the whole gradient: the TV launch adds to both tensors after the last render)
+        overlap = dp and self.diffuse and grid.storage != "reference" and gf is not None and not self.tv
         # ... and with equal chunks the exchange is split around a sharded Adam (reduce-scatter | update 1/N | all-gather)
         sharded = overlap and self.shard_optimizer and rfdist.can_shard(gd.numel()) and rfdist.can_shard(gf.numel())
         reduce_async = rfdist.reduce_scatter_mean_async if sharded else rfdist.all_reduce_mean_async
@@ -931,6 +1003,7 @@ class TrainStepper:
             if overlap and i == 0:
                 pending.append(reduce_async(self.flat.flat_gradient_parts()[1]))
         self._grad_clean = False
+        tv = self._add_tv_gradient()
         if overlap:
             pending.append(reduce_async(self.flat.flat_gradient_parts()[0]))
             for handle in pending:
@@ -950,7 +1023,7 @@ class TrainStepper:
             self.optimizer.step()
         self._grad_clean = False
         means = sums / float(3 * n)
-        return StepStats(means[0], means[2] if self.diffuse else None, means[1], means[3] if self.diffuse else None)
+        return StepStats(means[0], means[2] if self.diffuse else None, means[1], means[3] if self.diffuse else None, tv=tv)
 
     def _bin_buffers(self, n: int, S: int, device):
         b = self._bins
@@ -1025,6 +1098,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     storage: Optional[str] = "split",
     ray_selection: str = "keyed",
     global_batch: bool = False,
+    tv_density_weight: float = 0.0,
+    tv_feature_weight: float = 0.0,
+    tv_epsilon: float = 1e-8,
 ) -> VolumetricModel:
     """Same arguments (minus the feedback/visualisation ones) and same schedule as the reference's
     trainer.  Returns the trained model; ``history`` (if given) collects the logged scalars.
@@ -1032,7 +1108,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     None = keep the model's); checkpoints and ``.densities`` / ``.features`` stay in the reference layout and the
     returned model's grid is converted back to the storage it came in.
     ``global_batch`` (data parallel): ``ray_batch_size`` is split over the ranks instead of drawn per rank (seed all
-    ranks equally)."""
+    ranks equally).
+    ``tv_density_weight`` / ``tv_feature_weight`` / ``tv_epsilon``: total-variation regularisation of the grid in every stage
+    (TrainStepper); the summary lines then carry ``tv_density`` / ``tv_features``."""
     grid = vol_mod.thre3d_repr
     assert isinstance(grid, VoxelGrid), f"cannot use a {type(grid)} with this TrainProcedure"
     assert vol_mod.render_procedure is render_sh_voxel_grid, "non SH-based VoxelGrids cannot be used with this TrainProcedure"
@@ -1074,7 +1152,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
         data = stage_sets[stage - 1]
         batches = data.image_batches(image_batch_cache_size)
         lr = learning_rate * (stagewise_lr_decay_gamma ** (stage - 1))
-        stepper = TrainStepper(vol_mod, ray_batch_size, lr, apply_diffuse_render_regularization, ray_selection=ray_selection, global_batch=global_batch)
+        stepper = TrainStepper(vol_mod, ray_batch_size, lr, apply_diffuse_render_regularization, ray_selection=ray_selection, global_batch=global_batch,
+                               tv_density_weight=tv_density_weight, tv_feature_weight=tv_feature_weight, tv_epsilon=tv_epsilon)
         scheduler = ExponentialLR(stepper.optimizer, lr_decay_gamma_per_stage)
         if is_main:
             log(
@@ -1092,6 +1171,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 if stats.diffuse_loss is not None:
                     row["diffuse_loss"] = float(stats.diffuse_loss)
                 row.update(stats.psnr())
+                if stats.tv_density is not None:
+                    row["tv_density"], row["tv_features"] = float(stats.tv_density), float(stats.tv_features)
                 if history is not None:
                     history.append(row)
                 if is_main:
