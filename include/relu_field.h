@@ -427,6 +427,30 @@ int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream);
 int rf_tv_grad(const RFGrid* grid, float weight_density, float weight_features, float epsilon, float* grad_first_dev,
                float* grad_second_dev, float* sums_dev, void* stream);
 
+/* Visibility statistics of a trained field (what Plenoxels / DVGO prune their grids by): for every ray of the batch and every
+ * sample i the forward pass treats as inside the box, w_i = T_i * alpha_i exactly as rf_render_forward computes it (same sampling,
+ * jitter, first_ray / camera, RF_FLAG_AABB_SAMPLING and RF_FLAG_OCCUPANCY_SKIP handling, last interval 1e10), and for each of the 8
+ * corners k of the sample's cell with trilinear weight b_k:   M[n_k] = max(M[n_k], w_i * b_k)   (one float32 multiply; a product
+ * equal to 0 updates nothing).  max_weight_dev is [X, Y, Z] float32, z fastest, in PLAIN node order whatever grid->layout is; the
+ * caller owns and initialises it (normally zeros; finite values >= 0) and the call only RAISES entries: one call per view
+ * accumulates over views.  The update is an atomic max on the bit pattern behind a plain load, so the result does not depend on
+ * the order of arrival: bitwise reproducible.  RF_FLAG_WHITE_BKGD / RF_FLAG_RENDER_DIFFUSE are accepted and change nothing; only the
+ * density element of a node is read (split / bricked: of its base record), never a feature.  Every density mode, layout, F and
+ * num_samples >= 1.  Before any device access: RF_ERR_NULL_POINTER, RF_ERR_BAD_SHAPE (dims, num_samples < 1).  (Added to ABI
+ * version 4 compatibly: no existing struct or signature changed.) */
+int rf_node_max_weight(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float* max_weight_dev, void* stream);
+
+/* Prune by that statistic: keep(n) iff some node m inside the grid with |m - n|_inf <= dilate has M[m] > threshold (strict:
+ * threshold = 0 prunes exactly the nodes no sample ever weighted).  The raw density of a pruned node becomes min(D, fill_density)
+ * under RF_DENSITY_RELU / SOFTPLUS / IDENTITY (pruning never raises a density) and 0 under RF_DENSITY_ABS (fill_density != 0 is
+ * RF_ERR_BAD_SHAPE there).  densities_dev is the grid's own writable density / base tensor (strides and node order of `grid`);
+ * kept nodes, every feature and the padding nodes of bricked storage keep their bits.  keep_dev (optional, [X, Y, Z] bytes, plain
+ * node order) receives the mask; counts_dev (optional, 2 x int64) is ADDED to: (kept, pruned).  Gather form: one thread owns a
+ * node, no atomics but the two counters.  RF_ERR_BAD_SHAPE: dilate outside [0, 4], a negative or non-finite threshold, a NaN fill;
+ * RF_ERR_NULL_POINTER: grid, max_weight_dev, densities_dev.  (Added to ABI version 4 compatibly.) */
+int rf_prune_grid(const RFGrid* grid, const float* max_weight_dev, float threshold, int32_t dilate, float fill_density,
+                  float* densities_dev, uint8_t* keep_dev, int64_t* counts_dev, void* stream);
+
 /* Iso-surface extraction (csrc/mesh_kernels.hip; the contract -- field, lattice, Kuhn tetrahedra, edge keys, orientation and
  * canonical order -- is in that file's header and in DESIGN.md).  The level set sigma = iso_level of the grid's density on the
  * lattice of `subdivisions` (1..8) points per voxel and axis plus one guard plane on each AABB face, as a closed oriented mesh.

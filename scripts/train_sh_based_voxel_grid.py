@@ -42,6 +42,23 @@ def synthetic_dataset(dev, size, n_views, samples):
     return PosedImagesInMemory(images, pose_mat, intr, bounds)
 
 
+def load_datasets(config, dev):
+    """(train, test) from the data options: --synthetic / --synthetic_size, or --data_path (.npz), --data_downsample_factor; the
+    last two views are held out (scripts/prune_sh_based_voxel_grid.py takes the same options and the same split)"""
+    if config["synthetic"] or config["data_path"] is None:
+        data = synthetic_dataset(dev, config["synthetic_size"], 24, min(config["train_num_samples_per_ray"], 256))
+    else:
+        z = np.load(config["data_path"])
+        images = torch.from_numpy(z["images"]).float().to(dev)
+        intr = rf.CameraIntrinsics(images.shape[2], images.shape[3], float(z["focal"]))
+        data = PosedImagesInMemory(images, torch.from_numpy(z["poses"]).float().to(dev), intr, rf.CameraBounds(float(z["near"]), float(z["far"])))
+    if config["data_downsample_factor"] != 1.0:
+        data = data.downsampled(config["data_downsample_factor"])
+    test = PosedImagesInMemory(data.images[-2:], data.poses[-2:], data.camera_intrinsics, data.camera_bounds)
+    train = PosedImagesInMemory(data.images[:-2], data.poses[:-2], data.camera_intrinsics, data.camera_bounds)
+    return train, test
+
+
 # -------------------------------------------------------------------------------------
 #  Command line configuration for the script (option names / defaults of the reference) |
 # -------------------------------------------------------------------------------------
@@ -94,6 +111,9 @@ def synthetic_dataset(dev, size, n_views, samples):
 @click.option("--tv_density_weight", type=click.FLOAT, required=False, default=0.0, help="weight of the total variation of the raw densities (0: off)")
 @click.option("--tv_feature_weight", type=click.FLOAT, required=False, default=0.0, help="weight of the total variation of the SH features (0: off)")
 @click.option("--tv_epsilon", type=click.FLOAT, required=False, default=1e-8, help="epsilon inside the square root of the total variation")
+@click.option("--prune_threshold", type=click.FLOAT, required=False, default=-1.0,
+              help="at the end of every stage, empty the nodes whose largest compositing weight over the training views stays at or below this (negative: off)")
+@click.option("--prune_dilate", type=click.INT, required=False, default=1, help="nodes within this many steps of a node above the threshold are kept")
 @click.option("--seed", type=click.INT, required=False, default=42, help="seed of torch's generators")
 # fmt: on
 # -------------------------------------------------------------------------------------
@@ -106,17 +126,8 @@ def main(**kwargs) -> None:
     torch.cuda.set_device(dev)
     # ray selection draws from the CPU generator: equal seeds on all ranks for one global batch, distinct ones otherwise
     torch.manual_seed(config["seed"] if config["global_batch"] else config["seed"] + rank)
-    if config["synthetic"] or config["data_path"] is None:
-        data = synthetic_dataset(dev, config["synthetic_size"], 24, min(config["train_num_samples_per_ray"], 256))
-    else:
-        z = np.load(config["data_path"])
-        images = torch.from_numpy(z["images"]).float().to(dev)
-        intr = rf.CameraIntrinsics(images.shape[2], images.shape[3], float(z["focal"]))
-        data = PosedImagesInMemory(images, torch.from_numpy(z["poses"]).float().to(dev), intr, rf.CameraBounds(float(z["near"]), float(z["far"])))
-    if config["data_downsample_factor"] != 1.0:
-        data = data.downsampled(config["data_downsample_factor"])
-    test = PosedImagesInMemory(data.images[-2:], data.poses[-2:], data.camera_intrinsics, data.camera_bounds)
-    train = PosedImagesInMemory(data.images[:-2], data.poses[:-2], data.camera_intrinsics, data.camera_bounds)
+    train, test = load_datasets(config, dev)
+    data = train
 
     world_size = tuple(config["grid_world_size"])
     if config["use_relu_field"] and not config["use_softplus_field"]:  # the three configurations of the reference (:169-192)
@@ -144,7 +155,8 @@ def main(**kwargs) -> None:
         stagewise_lr_decay_gamma=config["stagewise_lr_decay_gamma"], save_freq=config["save_frequency"], test_freq=config["test_frequency"],
         summary_freq=config["summary_frequency"], apply_diffuse_render_regularization=config["apply_diffuse_render_regularization"],
         global_batch=config["global_batch"], tv_density_weight=config["tv_density_weight"], tv_feature_weight=config["tv_feature_weight"],
-        tv_epsilon=config["tv_epsilon"],
+        tv_epsilon=config["tv_epsilon"], prune_threshold=config["prune_threshold"] if config["prune_threshold"] >= 0.0 else None,
+        prune_dilate=config["prune_dilate"],
     )
 
 

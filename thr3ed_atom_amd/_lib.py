@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = [
     "rf_upsample_grid",
     "rf_convert_grid",
     "rf_tv_grad",
+    "rf_node_max_weight",
+    "rf_prune_grid",
     "rf_l1_loss_grad",
     "rf_adam_step",
     "rf_train_step",
@@ -309,6 +311,8 @@ def load() -> C.CDLL:
     lib.rf_upsample_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), vp]
     lib.rf_convert_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), vp]
     lib.rf_tv_grad.argtypes = [C.POINTER(RFGrid), f32, f32, f32, vp, vp, vp, vp]
+    lib.rf_node_max_weight.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, vp, vp]
+    lib.rf_prune_grid.argtypes = [C.POINTER(RFGrid), vp, f32, i32, f32, vp, vp, vp, vp]
     lib.rf_build_occupancy.argtypes = [C.POINTER(RFGrid), f32, vp, vp]
     lib.rf_l1_loss_grad.argtypes = [vp, vp, i64, f32, vp, vp, vp]
     lib.rf_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, vp]

@@ -4493,6 +4493,134 @@ __global__ __launch_bounds__(kWave * kTvRows) void tv_grad_kernel(GridArgs g, fl
   }
 }
 
+// =============================================================================================
+// rf_node_max_weight: per grid node the largest compositing weight any sample ever gave it.  The walk is
+// render_forward_ray's P0 without everything that depends on colour: one wave per ray, lanes = the samples of a 64-sample chunk, the
+// same helpers in the same order (load_ray, box_span / chunk_outside_box, z_of / sample_at, corners_of, the separately rounded density
+// sum in ATen's corner order, density_post, occupancy_alpha, the DPP transmittance scan), so w_i = alpha_i T_i is the forward's float
+// bit for bit.  No SH basis, no LDS work list, no cache.  Every corner k of an inside sample's cell offers v = w_i * cn.w[k] to
+// M[node]: an atomicMax on the bit pattern (integer order == float order for non-negative floats), behind a plain load that rejects
+// what cannot raise the entry -- a stale value read there is only ever too SMALL (entries never fall), which costs a redundant atomic
+// and never a wrong result.  A maximum does not depend on the order of arrival: bitwise reproducible.  M is in plain node order
+// ((x * Y + y) * Z + z) whatever the grid's storage.
+// GUARD / DEDUPE are measurement switches of tools/node_weights_time.py (compile-time: RF_NMW_GUARD, RF_NMW_DEDUPE).  DEDUPE: a
+// lane whose predecessor sampled the same cell and offers at least as much to a corner drops that corner's update (the relation is
+// transitive along a run of lanes, so the run's first lane still carries the maximum).
+// =============================================================================================
+#ifndef RF_NMW_GUARD
+#define RF_NMW_GUARD 1
+#endif
+#ifndef RF_NMW_DEDUPE
+#define RF_NMW_DEDUPE 0
+#endif
+
+template <bool GUARD, bool DEDUPE>
+__global__ __launch_bounds__(kBlock) void node_max_weight_kernel(GridArgs g, RayArgs r, uint32_t flags, unsigned int* M) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
+  if (ray >= r.n) return;  // (wave-uniform)
+
+  const RayState st = load_ray(r, g, ray, flags);
+  const bool use_occ = (flags & RF_FLAG_OCCUPANCY_SKIP) && g.occ != nullptr;
+  const BoxSpan span = box_span(st, r, g);
+  const unsigned int px = (unsigned)g.Y * (unsigned)g.Z, py = (unsigned)g.Z;  // plain node order of M
+  float T_carry = 1.0f;
+  const int nchunks = (r.S + kWave - 1) / kWave;
+  for (int chunk = 0; chunk < nchunks; ++chunk) {
+    if (chunk_outside_box(span, st, r, chunk)) continue;  // wave-uniform: sigma = 0 -> w = 0, T unchanged
+    const int s = chunk * kWave + lane;
+    const Sample sm = make_sample(st, r, g, ray, s);
+    bool live = sm.inside;
+    if (use_occ && live) live = cell_occupied(sm.cell, g);
+    float sigma = 0.0f;
+    Corners cn;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) cn.w[k] = 0.0f, cn.lin[k] = 0u;
+    cn.s[0] = cn.s[1] = cn.s[2] = 0u;
+    const uint32_t packed = pack_cell(sm.cell);
+    if (live) {
+      const float wts[6] = {sm.cell.w0[0], sm.cell.w1[0], sm.cell.w0[1], sm.cell.w1[1], sm.cell.w0[2], sm.cell.w1[2]};
+      cn = corners_of(packed, wts, g);
+      float pre;
+      sigma = interp_density(cn, g, pre);  // (reads element 0 of a node's density / base record only: no feature is touched)
+    }
+    float one_minus;
+    const float alpha = occupancy_alpha(sigma * sm.delta, one_minus);
+    float incl_e = sm.valid ? one_minus : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
+    wave_incl_scan_trans(incl_e, incl_a);
+    const float incl = prefix_transmittance(incl_e, incl_a);
+    const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
+    const float T = T_carry * excl;
+    const float w = live ? alpha * T : 0.0f;
+    T_carry = T_carry * read_lane(incl, kWave - 1);
+
+    // the cell's lower node in plain order; the steps collapse where corners_of's do (clamped at the border)
+    const int ix0 = (int)(packed & 0x7ffu) - 1, iy0 = (int)((packed >> 11) & 0x7ffu) - 1, iz0 = (int)(packed >> 22) - 1;
+    const unsigned int lin0 = ((unsigned)max(ix0, 0) * (unsigned)g.Y + (unsigned)max(iy0, 0)) * (unsigned)g.Z + (unsigned)max(iz0, 0);
+    const unsigned int sx = cn.s[0] ? px : 0u, sy = cn.s[1] ? py : 0u, sz = cn.s[2] ? 1u : 0u;
+    uint32_t prev_cell = 0u;
+    if constexpr (DEDUPE) {
+      const uint32_t tag = live ? packed : 0xffffffffu;  // (a live cell never packs to all ones: dims <= 2046)
+      prev_cell = (uint32_t)__builtin_amdgcn_update_dpp((int)0xfffffffeu, (int)tag, kDppWaveShr1, 0xf, 0xf, false);
+      prev_cell = (prev_cell == tag) ? 1u : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float v = w * cn.w[k];
+      bool offer = v > 0.0f;  // a product equal to 0 (or a NaN) updates nothing
+      if constexpr (DEDUPE) {
+        const float pv = dpp_move<kDppWaveShr1, 0xf>(0.0f, v);
+        offer = offer && !(prev_cell && pv >= v);
+      }
+      if (offer) {
+        unsigned int* p = M + (size_t)(lin0 + ((k & 1) ? sx : 0u) + ((k & 2) ? sy : 0u) + ((k & 4) ? sz : 0u));
+        if (!GUARD || v > __uint_as_float(*p)) atomicMax(p, __float_as_uint(v));
+      }
+    }
+    if (T_carry == 0.0f) break;  // every later weight is exactly 0
+  }
+}
+
+// rf_prune_grid: keep(n) = some node m of the grid with |m - n|_inf <= dilate has M[m] > threshold; a pruned node's raw density
+// is lowered to the fill.  GATHER form: one thread owns a node, reads the (2 dilate + 1)^3 neighbourhood of M (plain node order,
+// clipped to the grid) and writes only its own density element (node_lin: padding nodes of bricked storage are never addressed).
+// The two counters take one atomic add per wave.
+__global__ __launch_bounds__(256) void prune_grid_kernel(GridArgs g, const float* __restrict__ M, float threshold, int dilate, float fill,
+                                                         float* __restrict__ dens, unsigned char* __restrict__ keep_out,
+                                                         unsigned long long* __restrict__ counts, long long nodes) {
+  const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool real = n < nodes;
+  bool keep = false;
+  if (real) {
+    const int z = (int)(n % g.Z), y = (int)((n / g.Z) % g.Y), x = (int)(n / ((long long)g.Z * g.Y));
+    const int x0 = max(x - dilate, 0), x1 = min(x + dilate, g.X - 1), y0 = max(y - dilate, 0), y1 = min(y + dilate, g.Y - 1);
+    const int z0 = max(z - dilate, 0), z1 = min(z + dilate, g.Z - 1);
+    for (int xi = x0; xi <= x1 && !keep; ++xi)
+      for (int yi = y0; yi <= y1 && !keep; ++yi) {
+        const float* row = M + ((long long)xi * g.Y + yi) * g.Z;
+        for (int zi = z0; zi <= z1; ++zi) keep = keep || row[zi] > threshold;
+      }
+    if (keep_out) keep_out[n] = keep ? 1 : 0;
+    if (!keep) {
+      float* p = dens + (long long)node_lin(g, x, y, z) * g.dstride;
+      const float D = *p;
+      if (g.mode == RF_DENSITY_ABS) {
+        *p = 0.0f;
+      } else if (fill < D) {  // min(D, fill): pruning never raises a density (a density at or below the fill keeps its bits)
+        *p = fill;
+      }
+    }
+  }
+  if (counts) {
+    const unsigned long long kept = __popcll(__ballot(real && keep)), pruned = __popcll(__ballot(real && !keep));
+    if ((threadIdx.x & (kWave - 1)) == 0) {
+      if (kept) atomicAdd(counts + 0, kept);
+      if (pruned) atomicAdd(counts + 1, pruned);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ---------------------------------------------------------------------------------------------
@@ -5526,6 +5654,38 @@ int rf_tv_grad(const RFGrid* grid, float weight_density, float weight_features, 
     constexpr int KK = decltype(k)::value;
     return sums_dev ? launch(tv_grad_kernel<KK, 1, true>) : launch(tv_grad_kernel<KK, 1, false>);
   });
+}
+
+int rf_node_max_weight(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float* max_weight_dev, void* stream) {
+  int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  rc = check_rays(rays);
+  if (rc != RF_OK) return rc;
+  if (!max_weight_dev) return RF_ERR_NULL_POINTER;
+  if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
+  if (rays->num_rays == 0) return RF_OK;
+  const GridArgs g = to_args(grid);
+  const RayArgs r = to_args(rays, flags);
+  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
+  hipLaunchKernelGGL((node_max_weight_kernel<RF_NMW_GUARD != 0, RF_NMW_DEDUPE != 0>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags,
+                     reinterpret_cast<unsigned int*>(max_weight_dev));
+  return launch_status();
+}
+
+int rf_prune_grid(const RFGrid* grid, const float* max_weight_dev, float threshold, int32_t dilate, float fill_density, float* densities_dev,
+                  uint8_t* keep_dev, int64_t* counts_dev, void* stream) {
+  const int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  if (!max_weight_dev || !densities_dev) return RF_ERR_NULL_POINTER;
+  if (dilate < 0 || dilate > 4) return RF_ERR_BAD_SHAPE;
+  if (!(threshold >= 0.0f) || !std::isfinite(threshold)) return RF_ERR_BAD_SHAPE;
+  if (fill_density != fill_density) return RF_ERR_BAD_SHAPE;
+  if (grid->density_mode == RF_DENSITY_ABS && fill_density != 0.0f) return RF_ERR_BAD_SHAPE;  // |D| has one empty value
+  const GridArgs g = to_args(grid);
+  const long long nodes = (long long)g.X * g.Y * g.Z;
+  hipLaunchKernelGGL(prune_grid_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, max_weight_dev, threshold,
+                     (int)dilate, fill_density, densities_dev, keep_dev, reinterpret_cast<unsigned long long*>(counts_dev), nodes);
+  return launch_status();
 }
 
 int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream) {

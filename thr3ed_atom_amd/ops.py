@@ -1053,6 +1053,95 @@ def total_variation(grid: VoxelGrid, epsilon: float = 1e-8) -> Tuple[Tensor, Ten
     return _TotalVariation.apply(first, second, grid, float(epsilon))
 
 
+class RayBatch(NamedTuple):
+    """The rays of one rf_node_max_weight launch: a ray list (``origins`` / ``directions`` [N, 3]) or, with ``camera`` =
+    (height, width, focal, rotation [3,3], translation [3]), pixels [first_ray, first_ray + num_rays) of a posed pinhole camera
+    generated inside the kernel (default: the whole frame).  ``t_rand``: None, a [N, S] tensor or a KeyedJitter."""
+
+    origins: Optional[Tensor]
+    directions: Optional[Tensor]
+    num_samples: int
+    near: float
+    far: float
+    t_rand: object = None
+    camera: Optional[tuple] = None
+    first_ray: int = 0
+    num_rays: Optional[int] = None
+
+
+def _camera_struct(height, width, focal, rotation, translation) -> "_lib.RFCamera":
+    cam = _lib.RFCamera()
+    cam.height, cam.width, cam.focal = int(height), int(width), float(np.float32(focal))
+    rot = torch.as_tensor(rotation).detach().to("cpu", torch.float32).reshape(3, 3)
+    trans = torch.as_tensor(translation).detach().to("cpu", torch.float32).reshape(3)
+    for i in range(3):
+        for j in range(3):
+            cam.pose[4 * i + j] = float(rot[i, j])
+        cam.pose[4 * i + 3] = float(trans[i])
+    return cam
+
+
+def _check_node_buffer(grid: VoxelGrid, t: Tensor, dtype, name: str) -> None:
+    _require_hip(t, name)
+    if tuple(t.shape) != tuple(grid.grid_dims) or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(grid.grid_dims)} (plain node order), got {t.dtype} {tuple(t.shape)}")
+
+
+def node_max_weight_raw(grid: VoxelGrid, rays: RayBatch, flags: int, out: Tensor) -> None:
+    """Enqueue rf_node_max_weight: raise ``out`` [X, Y, Z] (float32, plain node order, caller-initialised) to the largest
+    compositing weight x trilinear weight any sample of ``rays`` gives each node (include/relu_field.h).  No autograd."""
+    lib = _lib.load()
+    _check_node_buffer(grid, out, torch.float32, "the max-weight buffer")
+    dev = out.device
+    if rays.camera is not None:
+        cam = _camera_struct(*rays.camera)
+        rb = _lib.RFRayBatch()
+        rb.num_rays = cam.height * cam.width - int(rays.first_ray) if rays.num_rays is None else int(rays.num_rays)
+        rb.num_samples, rb.near, rb.far = int(rays.num_samples), rays.near, rays.far
+        tv = t_vals_for(rays.num_samples, dev)
+        rb.t_vals_dev = tv.data_ptr()
+        rb.first_ray = int(rays.first_ray)
+        rb.camera = C.pointer(cam)
+        if isinstance(rays.t_rand, KeyedJitter):
+            rb.jitter_key = int(rays.t_rand.key) & 0xFFFFFFFFFFFFFFFF
+        elif rays.t_rand is not None:
+            rb.t_rand_dev = rays.t_rand.data_ptr()
+    else:
+        for name, t in (("ray origins", rays.origins), ("ray directions", rays.directions)):
+            _require_hip(t, name)
+            if not (t.is_contiguous() and t.dtype == torch.float32):
+                raise ValueError("rf_node_max_weight takes contiguous float32 rays")
+        rb, tv = _ray_batch(rays.origins, rays.directions, rays.num_samples, rays.near, rays.far, rays.t_rand)
+    use_occ = bool(int(flags) & _lib.FLAG_OCCUPANCY_SKIP)
+    rf_grid = grid.to_rf_grid(use_occupancy=use_occ)  # (only a node's density element is read: no shadow needed)
+    with _span("node_max_weight", dev):
+        rc = lib.rf_node_max_weight(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, rays.t_rand), out.data_ptr(), _stream(dev))
+    _lib.check(rc, "rf_node_max_weight")
+
+
+def prune_grid_raw(grid: VoxelGrid, max_weight: Tensor, threshold: float, dilate: int, fill_density: float, keep: Optional[Tensor] = None,
+                   counts: Optional[Tensor] = None) -> None:
+    """Enqueue rf_prune_grid on the grid's own density / base tensor, in place: nodes without a neighbour (Chebyshev distance
+    <= ``dilate``) whose ``max_weight`` exceeds ``threshold`` get the raw density min(D, fill_density) (0 under |.|).  ``keep``
+    (optional uint8 [X, Y, Z]) receives the mask, ``counts`` (optional int64 [2]) is added to: (kept, pruned).  The caller refreshes
+    what depends on the densities (``pruning.prune_voxel_grid`` does)."""
+    lib = _lib.load()
+    _check_node_buffer(grid, max_weight, torch.float32, "max_weight")
+    if keep is not None:
+        _check_node_buffer(grid, keep, torch.uint8, "the keep mask")
+    if counts is not None:
+        _require_hip(counts, "counts")
+        if counts.dtype != torch.int64 or counts.numel() < 2 or not counts.is_contiguous():
+            raise ValueError("counts must hold two int64")
+    first, _ = grid.kernel_tensors()
+    _require_hip(first, "grid tensor")
+    rf_grid = grid.to_rf_grid()
+    with _span("prune_grid", first.device):
+        rc = lib.rf_prune_grid(C.byref(rf_grid), max_weight.data_ptr(), float(threshold), int(dilate), float(fill_density), first.data_ptr(),
+                               _ptr(keep), _ptr(counts), _stream(first.device))
+    _lib.check(rc, "rf_prune_grid")
+
+
 def render_flags(white_bkgd: bool, render_diffuse: bool, optimized_sampling: bool, use_occupancy: bool) -> int:
     flags = 0
     flags |= _lib.FLAG_WHITE_BKGD if white_bkgd else 0

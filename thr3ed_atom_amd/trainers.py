@@ -1101,6 +1101,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     tv_density_weight: float = 0.0,
     tv_feature_weight: float = 0.0,
     tv_epsilon: float = 1e-8,
+    prune_threshold: Optional[float] = None,
+    prune_dilate: int = 1,
 ) -> VolumetricModel:
     """Same arguments (minus the feedback/visualisation ones) and same schedule as the reference's
     trainer.  Returns the trained model; ``history`` (if given) collects the logged scalars.
@@ -1110,7 +1112,11 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     ``global_batch`` (data parallel): ``ray_batch_size`` is split over the ranks instead of drawn per rank (seed all
     ranks equally).
     ``tv_density_weight`` / ``tv_feature_weight`` / ``tv_epsilon``: total-variation regularisation of the grid in every stage
-    (TrainStepper); the summary lines then carry ``tv_density`` / ``tv_features``."""
+    (TrainStepper); the summary lines then carry ``tv_density`` / ``tv_features``.
+    ``prune_threshold`` (None = off: nothing is launched or allocated) / ``prune_dilate``: at the end of every stage -- before the
+    grid is upsampled, and once after the last stage -- the nodes whose largest compositing weight over the stage's training views
+    stays at or below the threshold are emptied (pruning.node_max_weights + prune_voxel_grid); ``history`` gets a row with the
+    counts.  The stepper and the optimizer state are rebuilt per stage anyway, so no moments need handling."""
     grid = vol_mod.thre3d_repr
     assert isinstance(grid, VoxelGrid), f"cannot use a {type(grid)} with this TrainProcedure"
     assert vol_mod.render_procedure is render_sh_voxel_grid, "non SH-based VoxelGrids cannot be used with this TrainProcedure"
@@ -1191,6 +1197,17 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 save(f"model_stage_{stage}_iter_{global_step}.pth")
                 last = time.perf_counter()
         stepper.flat.detach()
+        if prune_threshold is not None:
+            from .pruning import node_max_weights, prune_voxel_grid
+
+            cfg = vol_mod.render_config
+            weights = node_max_weights(vol_mod.thre3d_repr, data.poses, data.camera_intrinsics, data.camera_bounds, cfg.num_samples_per_ray, render_config=cfg)
+            pruned = prune_voxel_grid(vol_mod.thre3d_repr, weights, prune_threshold, prune_dilate)
+            row = {"stage": stage, "pruned_nodes": pruned.pruned, "kept_nodes": pruned.kept}
+            if history is not None:
+                history.append(row)
+            if is_main:
+                log(f"pruned {pruned.pruned} of {pruned.pruned + pruned.kept} nodes after stage {stage} (threshold {prune_threshold}, dilate {prune_dilate})")
         if stage != num_stages:
             with torch.no_grad():
                 vol_mod.thre3d_repr = scale_voxel_grid_with_required_output_size(
