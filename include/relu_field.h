@@ -451,6 +451,28 @@ int rf_node_max_weight(const RFGrid* grid, const RFRayBatch* rays, uint32_t flag
 int rf_prune_grid(const RFGrid* grid, const float* max_weight_dev, float threshold, int32_t dilate, float fill_density,
                   float* densities_dev, uint8_t* keep_dev, int64_t* counts_dev, void* stream);
 
+/* Distortion loss of the rendered rays (mip-NeRF 360; DVGOv2's O(S) form): the regulariser that acts ALONG the ray and pulls its
+ * compositing weights into one compact interval.  For every ray of the batch, with the samples i = 0 .. S-1 and the weights
+ * w_i = T_i * alpha_i exactly as rf_render_forward computes them (same sampling, t_rand_dev / jitter key, first_ray / camera,
+ * RF_FLAG_AABB_SAMPLING and RF_FLAG_OCCUPANCY_SKIP handling, last interval 1e10; w_i = 0 for samples outside the box),
+ * s_i = (z_i - near) / (far - near) with the near / far of `rays` (the camera bounds, also under AABB sampling), and sample i
+ * standing for the interval it composites over:
+ *   i < S-1: d_i = s_{i+1} - s_i, m_i = (s_i + s_{i+1}) / 2;     i = S-1: d_i = 0, m_i = s_{S-1}   (the 1e10 interval has no width here)
+ *   l = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i                                    (num_samples == 1: l = 0)
+ * loss_dev (optional, [N]) is OVERWRITTEN with the unweighted l_r.  grad_first_dev (optional) follows the layout of `grid` like every
+ * gradient buffer of this ABI (split / bricked: the base record, whose element 0 is the density) and is ADDED to with
+ *   scale * grad_loss_dev[r] * d l_r / d D      (grad_loss_dev NULL: 1)
+ * for the RAW density parameter D only (through the activation, density_scale, sign(D) under RF_DENSITY_ABS and the trilinear
+ * weights, like the density lane of rf_render_backward): features do not enter, RF_FLAG_WHITE_BKGD / RF_FLAG_RENDER_DIFFUSE are
+ * accepted and change nothing, and NO gradient goes to rays or poses.  Float atomics: the sum order is not fixed; l itself is
+ * bitwise reproducible.  Only samples whose gradient is non-zero touch memory; padding nodes of bricked storage are never addressed.
+ * Both outputs NULL, scale == 0 without loss_dev, or zero rays: nothing is launched, RF_OK.  The kernel needs no scratch memory for
+ * any num_samples >= 1.  Before any device access: RF_ERR_NULL_POINTER (grid, its tensors, the rays' tensors, RF_FLAG_OCCUPANCY_SKIP
+ * without a mask), RF_ERR_BAD_SHAPE (dims, num_samples < 1, far == near, non-finite near / far / scale, a gradient pointer that IS
+ * the density tensor).  (Added to ABI version 4 compatibly: no existing struct or signature changed.) */
+int rf_distortion(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float scale, const float* grad_loss_dev, float* loss_dev,
+                  float* grad_first_dev, void* stream);
+
 /* Iso-surface extraction (csrc/mesh_kernels.hip; the contract -- field, lattice, Kuhn tetrahedra, edge keys, orientation and
  * canonical order -- is in that file's header and in DESIGN.md).  The level set sigma = iso_level of the grid's density on the
  * lattice of `subdivisions` (1..8) points per voxel and axis plus one guard plane on each AABB face, as a closed oriented mesh.

@@ -4582,6 +4582,181 @@ __global__ __launch_bounds__(kBlock) void node_max_weight_kernel(GridArgs g, Ray
   }
 }
 
+// =============================================================================================
+// rf_distortion: the distortion loss of a ray's compositing weights.  With the forward's samples and weights
+// w_i = T_i alpha_i (the walk of node_max_weight_kernel: same helpers, same order, no colour), s_i = (z_i - near) / (far - near) of the
+// batch's own bounds, and sample i standing for the interval it composites over (d_i = s_{i+1} - s_i, m_i = (s_i + s_{i+1}) / 2; the last
+// sample: d = 0, m = s):
+//   l = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+// The m_i are sorted, so with the exclusive prefixes A_i = sum_{j<i} w_j, B_i = sum_{j<i} w_j m_j and the totals W, WM:
+//   l = 2 sum_i w_i (m_i A_i - B_i) + (1/3) sum_i w_i^2 d_i                                           (prefixes only: pass 1)
+//   e_i = dl/dw_i = 2 [ m_i (A_i - (W - A_i - w_i)) - (B_i - (WM - B_i - w_i m_i)) ] + (2/3) w_i d_i   (needs the totals: pass 2)
+//   dl/dsigma_i = delta_i ( T_{i+1} e_i - sum_{j>i} w_j e_j )      -- render_backward_kernel's adjoint with this e_i
+// One wave per ray, lanes = the samples of a 64-sample chunk.  Pass 1 walks near to far (stops where the carried T is exactly 0) and
+// leaves each chunk's (T, A, B) carry in a per-wave LDS stash; pass 2 (GRAD) walks far to near with a true running suffix sum,
+// evaluates each chunk again from its carry and scatters 8 float atomics per sample whose gradient is non-zero onto the density
+// element.  Chunks beyond the stash (S > 64 kDistStash) get their carry by walking forward again from the last stashed one: correct
+// for every S, quadratic only in the chunks above the capacity.
+// =============================================================================================
+constexpr int kDistStash = 16;  // chunks whose carry is kept in LDS: 1024 samples per ray
+
+// inclusive PREFIX sum over the wave (DPP: four row_shr steps inside each row of 16 lanes, row_bcast:15 / :31 fold the rows)
+__device__ __forceinline__ float wave_incl_scan_add(float x) {
+  x += dpp_move<kDppRowShr1, 0xf>(0.0f, x);
+  x += dpp_move<kDppRowShr2, 0xf>(0.0f, x);
+  x += dpp_move<kDppRowShr4, 0xf>(0.0f, x);
+  x += dpp_move<kDppRowShr8, 0xf>(0.0f, x);
+  x += dpp_move<kDppRowBcast15, 0xa>(0.0f, x);
+  x += dpp_move<kDppRowBcast31, 0xc>(0.0f, x);
+  return x;
+}
+
+struct DistCarry {
+  float T, A, B;  // transmittance in front of the chunk, sum of w and of w m over the samples in front of it
+};
+
+// everything one lane knows about its sample of a chunk, given the chunk's carry
+struct DistChunk {
+  float w, m, d, A, B;   // weight, interval mid-point and width, exclusive prefixes (carry included)
+  float delta, sigma, Tn;  // interval length, activated density, T_{i+1} = T_i exp(-sigma_i delta_i)
+  bool live;
+  Corners cn;
+  DistCarry next;  // the carry behind the chunk (wave-uniform)
+};
+
+__device__ __forceinline__ DistChunk dist_chunk(const GridArgs& g, const RayArgs& r, const RayState& st, long long ray, int chunk, int lane,
+                                                bool use_occ, float inv_span, const DistCarry& in) {
+  DistChunk c;
+  const int s = chunk * kWave + lane;
+  const float z = z_of(st, r, ray, s), zn = z_of(st, r, ray, s + 1);
+  const Sample sm = sample_at(st, r, g, s, z, zn);  // == make_sample
+  bool live = sm.inside;
+  if (use_occ && live) live = cell_occupied(sm.cell, g);
+  float sigma = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) c.cn.w[k] = 0.0f, c.cn.lin[k] = 0u;
+  c.cn.s[0] = c.cn.s[1] = c.cn.s[2] = 0u;
+  if (live) {
+    const float wts[6] = {sm.cell.w0[0], sm.cell.w1[0], sm.cell.w0[1], sm.cell.w1[1], sm.cell.w0[2], sm.cell.w1[2]};
+    c.cn = corners_of(pack_cell(sm.cell), wts, g);
+    float pre;
+    sigma = interp_density(c.cn, g, pre);
+  }
+  float E;
+  const float alpha = occupancy_alpha(sigma * sm.delta, E);
+  float incl_e = sm.valid ? E : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
+  wave_incl_scan_trans(incl_e, incl_a);
+  const float incl = prefix_transmittance(incl_e, incl_a);
+  const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
+  const float T = in.T * excl;
+  c.w = live ? alpha * T : 0.0f;
+  c.Tn = T * E;
+  c.delta = sm.delta;
+  c.sigma = sigma;
+  c.live = live;
+  // the interval of the sample on the batch's own [near, far] (the camera bounds, also under AABB sampling)
+  const float s0 = (z - r.near) * inv_span, s1 = (zn - r.near) * inv_span;
+  const bool last = s >= r.S - 1;
+  c.d = last ? 0.0f : s1 - s0;
+  c.m = last ? s0 : 0.5f * (s0 + s1);
+  const float wm = c.w * c.m;
+  const float iw = wave_incl_scan_add(c.w), iwm = wave_incl_scan_add(wm);
+  c.A = in.A + (iw - c.w);
+  c.B = in.B + (iwm - wm);
+  c.next.T = in.T * read_lane(incl, kWave - 1);
+  c.next.A = in.A + read_lane(iw, kWave - 1);
+  c.next.B = in.B + read_lane(iwm, kWave - 1);
+  return c;
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(kBlock) void distortion_kernel(GridArgs g, RayArgs r, uint32_t flags, float scale, const float* __restrict__ gloss,
+                                                            float* __restrict__ loss, float* __restrict__ gdens) {
+  __shared__ float s_stash[GRAD ? kWavesPerBlock : 1][kDistStash][3];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
+  if (ray >= r.n) return;  // (wave-uniform)
+
+  float factor = scale;
+  if (GRAD && gloss) factor *= gloss[ray];
+  const bool want_grad = GRAD && factor != 0.0f;
+  if (!want_grad && !loss) return;
+
+  const RayState st = load_ray(r, g, ray, flags);
+  const bool use_occ = (flags & RF_FLAG_OCCUPANCY_SKIP) && g.occ != nullptr;
+  const BoxSpan span = box_span(st, r, g);
+  const float inv_span = 1.0f / (r.far - r.near);
+  const int nchunks = (r.S + kWave - 1) / kWave;
+
+  // pass 1, near to far: the loss from prefixes, the totals, every chunk's carry
+  DistCarry carry = {1.0f, 0.0f, 0.0f};
+  float part = 0.0f;  // this lane's share of l
+  int last_chunk = -1;
+  for (int chunk = 0; chunk < nchunks; ++chunk) {
+    if (GRAD && chunk < kDistStash && lane == 0) {
+      s_stash[wave][chunk][0] = carry.T;
+      s_stash[wave][chunk][1] = carry.A;
+      s_stash[wave][chunk][2] = carry.B;
+    }
+    if (chunk_outside_box(span, st, r, chunk)) continue;  // wave-uniform: w = 0 for the whole chunk, the carry unchanged
+    const DistChunk c = dist_chunk(g, r, st, ray, chunk, lane, use_occ, inv_span, carry);
+    part += 2.0f * c.w * (c.m * c.A - c.B) + (1.0f / 3.0f) * (c.w * c.w) * c.d;
+    carry = c.next;
+    last_chunk = chunk;
+    if (carry.T == 0.0f) break;  // every later weight is exactly 0
+  }
+  if (loss) {
+    const float total = wave_sum(part);
+    if (lane == 0) loss[ray] = total;
+  }
+  if (!want_grad) return;
+  if constexpr (GRAD) {
+    wave_lds_fence();
+    const float W = carry.A, WM = carry.B;
+    float suffix = 0.0f;  // sum of w_j e_j over all samples beyond the current chunk
+    // pass 2, far to near
+    for (int chunk = last_chunk; chunk >= 0; --chunk) {
+      if (chunk_outside_box(span, st, r, chunk)) continue;
+      const int have = min(chunk, kDistStash - 1);
+      DistCarry in = {s_stash[wave][have][0], s_stash[wave][have][1], s_stash[wave][have][2]};
+      for (int k = have; k < chunk; ++k) {  // beyond the stash: walk forward again from the last stashed carry
+        if (chunk_outside_box(span, st, r, k)) continue;
+        in = dist_chunk(g, r, st, ray, k, lane, use_occ, inv_span, in).next;
+      }
+      const DistChunk c = dist_chunk(g, r, st, ray, chunk, lane, use_occ, inv_span, in);
+      const float wm = c.w * c.m;
+      const float e = 2.0f * (c.m * (c.A - ((W - c.A) - c.w)) - (c.B - ((WM - c.B) - wm))) + (2.0f / 3.0f) * (c.w * c.d);
+      const float we = c.w * e;  // (0 for lanes beyond the ray's last sample and for samples outside the box: w = 0)
+      const float incl = wave_incl_rscan_add(we, lane);
+      const float after = (incl - we) + suffix;  // sum over samples strictly behind this one
+      suffix += __shfl(incl, 0, kWave);
+      const float g_sigma = c.delta * (c.Tn * e - after);
+      float g_pre;
+      if (g.mode == RF_DENSITY_RELU)
+        g_pre = (c.sigma > 0.0f) ? g_sigma : 0.0f;
+      else if (g.mode == RF_DENSITY_SOFTPLUS)
+        g_pre = g_sigma * softplus_slope(c.sigma);
+      else
+        g_pre = g_sigma;
+      g_pre *= factor;
+      if (c.live && g_pre != 0.0f) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          // (a corner outside the grid has weight 0 and the clamped index of a real node: nothing is added, nothing out of range is read)
+          const size_t at = (size_t)c.cn.lin[k] * (size_t)g.dstride;
+          float gv = (c.cn.w[k] * g_pre) * g.rho;
+          if (g.mode == RF_DENSITY_ABS) {
+            const float dv = g.dens[at] * g.rho;
+            gv = (dv > 0.f) ? gv : ((dv < 0.f) ? -gv : 0.0f);
+          }
+          if (gv != 0.0f) unsafeAtomicAdd(gdens + at, gv);
+        }
+      }
+    }
+  }
+}
+
 // rf_prune_grid: keep(n) = some node m of the grid with |m - n|_inf <= dilate has M[m] > threshold; a pruned node's raw density
 // is lowered to the fill.  GATHER form: one thread owns a node, reads the (2 dilate + 1)^3 neighbourhood of M (plain node order,
 // clipped to the grid) and writes only its own density element (node_lin: padding nodes of bricked storage are never addressed).
@@ -5669,6 +5844,30 @@ int rf_node_max_weight(const RFGrid* grid, const RFRayBatch* rays, uint32_t flag
   const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
   hipLaunchKernelGGL((node_max_weight_kernel<RF_NMW_GUARD != 0, RF_NMW_DEDUPE != 0>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags,
                      reinterpret_cast<unsigned int*>(max_weight_dev));
+  return launch_status();
+}
+
+int rf_distortion(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float scale, const float* grad_loss_dev, float* loss_dev,
+                  float* grad_first_dev, void* stream) {
+  int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  rc = check_rays(rays);
+  if (rc != RF_OK) return rc;
+  if (!std::isfinite(rays->near) || !std::isfinite(rays->far) || rays->far == rays->near || !std::isfinite(scale)) return RF_ERR_BAD_SHAPE;
+  if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
+  // the gradient is added to a tensor of its own, never to the parameters
+  if (grad_first_dev && grad_first_dev == grid->densities_dev) return RF_ERR_BAD_SHAPE;
+  const bool want_grad = grad_first_dev != nullptr && scale != 0.0f;
+  if ((!want_grad && !loss_dev) || rays->num_rays == 0) return RF_OK;
+  const GridArgs g = to_args(grid);
+  const RayArgs r = to_args(rays, flags);
+  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
+  if (want_grad)
+    hipLaunchKernelGGL(distortion_kernel<true>, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, scale, grad_loss_dev, loss_dev,
+                       grad_first_dev);
+  else
+    hipLaunchKernelGGL(distortion_kernel<false>, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, 0.0f, (const float*)nullptr, loss_dev,
+                       (float*)nullptr);
   return launch_status();
 }
 

@@ -1087,12 +1087,8 @@ def _check_node_buffer(grid: VoxelGrid, t: Tensor, dtype, name: str) -> None:
         raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(grid.grid_dims)} (plain node order), got {t.dtype} {tuple(t.shape)}")
 
 
-def node_max_weight_raw(grid: VoxelGrid, rays: RayBatch, flags: int, out: Tensor) -> None:
-    """Enqueue rf_node_max_weight: raise ``out`` [X, Y, Z] (float32, plain node order, caller-initialised) to the largest
-    compositing weight x trilinear weight any sample of ``rays`` gives each node (include/relu_field.h).  No autograd."""
-    lib = _lib.load()
-    _check_node_buffer(grid, out, torch.float32, "the max-weight buffer")
-    dev = out.device
+def _ray_batch_struct(rays: RayBatch, dev, what: str):
+    """The RFRayBatch of a RayBatch and what must stay alive until the launch is enqueued (the camera struct, t_vals)."""
     if rays.camera is not None:
         cam = _camera_struct(*rays.camera)
         rb = _lib.RFRayBatch()
@@ -1106,17 +1102,131 @@ def node_max_weight_raw(grid: VoxelGrid, rays: RayBatch, flags: int, out: Tensor
             rb.jitter_key = int(rays.t_rand.key) & 0xFFFFFFFFFFFFFFFF
         elif rays.t_rand is not None:
             rb.t_rand_dev = rays.t_rand.data_ptr()
-    else:
-        for name, t in (("ray origins", rays.origins), ("ray directions", rays.directions)):
-            _require_hip(t, name)
-            if not (t.is_contiguous() and t.dtype == torch.float32):
-                raise ValueError("rf_node_max_weight takes contiguous float32 rays")
-        rb, tv = _ray_batch(rays.origins, rays.directions, rays.num_samples, rays.near, rays.far, rays.t_rand)
+        return rb, (cam, tv)
+    for name, t in (("ray origins", rays.origins), ("ray directions", rays.directions)):
+        _require_hip(t, name)
+        if not (t.is_contiguous() and t.dtype == torch.float32):
+            raise ValueError(f"{what} takes contiguous float32 rays")
+    rb, tv = _ray_batch(rays.origins, rays.directions, rays.num_samples, rays.near, rays.far, rays.t_rand)
+    return rb, (tv,)
+
+
+def node_max_weight_raw(grid: VoxelGrid, rays: RayBatch, flags: int, out: Tensor) -> None:
+    """Enqueue rf_node_max_weight: raise ``out`` [X, Y, Z] (float32, plain node order, caller-initialised) to the largest
+    compositing weight x trilinear weight any sample of ``rays`` gives each node (include/relu_field.h).  No autograd."""
+    lib = _lib.load()
+    _check_node_buffer(grid, out, torch.float32, "the max-weight buffer")
+    dev = out.device
+    rb, keep = _ray_batch_struct(rays, dev, "rf_node_max_weight")
     use_occ = bool(int(flags) & _lib.FLAG_OCCUPANCY_SKIP)
     rf_grid = grid.to_rf_grid(use_occupancy=use_occ)  # (only a node's density element is read: no shadow needed)
     with _span("node_max_weight", dev):
         rc = lib.rf_node_max_weight(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, rays.t_rand), out.data_ptr(), _stream(dev))
+    del keep
     _lib.check(rc, "rf_node_max_weight")
+
+
+def distortion_raw(grid: VoxelGrid, rays: RayBatch, flags: int, scale: float = 1.0, grad_loss: Optional[Tensor] = None, loss: Optional[Tensor] = None,
+                   grad_first: Optional[Tensor] = None) -> None:
+    """Enqueue rf_distortion (include/relu_field.h): the distortion loss of the compositing weights of ``rays`` as the forward render
+    with the same ``flags`` and jitter sees them.  ``loss`` [N] (optional) is OVERWRITTEN with the unweighted per-ray values;
+    ``grad_first`` (optional, the shape of ``grid.kernel_tensors()[0]``) is ADDED to with ``scale * grad_loss[r] * d l_r / d D`` for
+    the raw density (``grad_loss`` [N] or None = 1).  The gradient reaches the densities only: none goes to features, rays or poses.
+    No autograd: ``distortion_loss`` is the differentiable form."""
+    lib = _lib.load()
+    first, _ = grid.kernel_tensors()
+    _require_hip(first, "grid tensor")
+    dev = first.device
+    rb, keep = _ray_batch_struct(rays, dev, "rf_distortion")
+    n = int(rb.num_rays)
+    for name, t in (("grad_loss", grad_loss), ("loss", loss)):
+        if t is not None:
+            _require_hip(t, name)
+            if not (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n):
+                raise ValueError(f"rf_distortion: {name} must be a contiguous float32 tensor of one value per ray ({n})")
+    if grad_first is not None:
+        _require_hip(grad_first, "gradient tensor")
+        if not (grad_first.is_contiguous() and grad_first.dtype == torch.float32 and tuple(grad_first.shape) == tuple(first.shape)):
+            raise ValueError("rf_distortion: the gradient tensor must be contiguous float32 with the shape of grid.kernel_tensors()[0]")
+    use_occ = bool(int(flags) & _lib.FLAG_OCCUPANCY_SKIP)
+    rf_grid = grid.to_rf_grid(use_occupancy=use_occ)  # (only a node's density element is read: no shadow needed)
+    with _span("distortion", dev):
+        rc = lib.rf_distortion(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, rays.t_rand), float(scale), _ptr(grad_loss), _ptr(loss),
+                               _ptr(grad_first), _stream(dev))
+    del keep
+    _lib.check(rc, "rf_distortion")
+
+
+class _DistortionLoss(torch.autograd.Function):
+    """L = mean over the rays of the distortion loss.  Forward: one launch for the per-ray values only.  Backward: one launch with
+    scale = upstream / N that adds into the grid's gradient bucket when it has one (returning None like _ReluFieldRender), else into
+    a fresh tensor of the density parameter's layout.  No gradient to features, rays or poses."""
+
+    @staticmethod
+    def forward(ctx, first, grid: VoxelGrid, rays: RayBatch, flags):
+        _require_hip(first, "grid tensor")
+        per_ray = torch.empty(int(_ray_batch_struct(rays, first.device, "rf_distortion")[0].num_rays), dtype=torch.float32, device=first.device)
+        distortion_raw(grid, rays, flags, 0.0, None, per_ray, None)
+        ctx.grid, ctx.rays, ctx.flags, ctx.n = grid, rays, int(flags), per_ray.numel()
+        ctx.save_for_backward(first)
+        ctx.set_materialize_grads(False)
+        return per_ray.sum() / max(per_ray.numel(), 1)
+
+    @staticmethod
+    def backward(ctx, g_loss):
+        (first,) = ctx.saved_tensors
+        grid: VoxelGrid = ctx.grid
+        if g_loss is None or ctx.n == 0:
+            return None, None, None, None
+        _check_tensors_current(grid, first, grid.kernel_tensors()[1])
+        scale = float(g_loss) / ctx.n  # (the scale crosses the C ABI by value: reading the upstream scalar is one host synchronisation)
+        bucket = getattr(grid, "_grad_bucket", None)
+        if bucket is not None and bucket.matches(*grid.kernel_tensors()):
+            if getattr(bucket, "deferred", False):
+                raise RuntimeError("deferred gradients (optim.FlatGrid(deferred=True)) carry record lists only: distortion_loss needs FlatGrid(deferred=False)")
+            gd, _ = bucket.views_for_accumulation()
+            ret = bucket.autograd_return()[0]
+        else:
+            gd = torch.zeros_like(first)
+            ret = gd
+        distortion_raw(grid, ctx.rays, ctx.flags, scale, None, None, gd)
+        return ret, None, None, None
+
+
+def distortion_loss(grid_or_model, rays, num_samples: int, bounds, *, perturb: bool = False, t_rand=None, jitter_key: Optional[int] = None,
+                    optimized_sampling: bool = False, use_occupancy: bool = False) -> Tensor:
+    """The distortion loss of mip-NeRF 360 on the compositing weights of ``rays`` (a Rays-like object with flat ``origins`` /
+    ``directions`` [N, 3]) as a differentiable 0-d tensor: L = mean over the rays of
+
+        l = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+
+    with the samples and weights w_i of a render of ``num_samples`` samples between ``bounds`` (a CameraBounds or (near, far)),
+    sample i standing for the normalised interval [s_i, s_{i+1}] it composites over (include/relu_field.h: rf_distortion).  The
+    jitter: ``t_rand`` (a [N, S] tensor or a KeyedJitter), else ``jitter_key`` (a KeyedJitter of that key), else with ``perturb`` a
+    freshly drawn key, else none -- pass the render's own to regularise the weights that render used.  ``grid_or_model``: a
+    VoxelGrid on any storage, a VolumetricModel, or a module with the reference VoxelGrid's attribute names.  One HIP launch forward,
+    one backward; the backward adds into the grid's gradient bucket (optim.FlatGrid) when it has one.  The gradient reaches the raw
+    densities only: none goes to the features, and none to rays or poses (``rays`` are used detached)."""
+    grid = as_kernel_grid(getattr(grid_or_model, "thre3d_repr", grid_or_model))
+    near, far = (bounds.near, bounds.far) if hasattr(bounds, "near") else bounds
+    origins = rays.origins.detach().to(torch.float32).contiguous()
+    directions = rays.directions.detach().to(torch.float32).contiguous()
+    if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
+        raise AssertionError("distortion_loss takes FLAT rays [N, 3]")
+    if t_rand is None:
+        if jitter_key is not None:
+            t_rand = KeyedJitter(int(jitter_key), 0)
+        elif perturb:
+            t_rand = KeyedJitter(draw_jitter_key(), 0)
+    elif not isinstance(t_rand, KeyedJitter):
+        t_rand = t_rand.detach().to(origins.device, torch.float32).contiguous()
+        if tuple(t_rand.shape) != (origins.shape[0], int(num_samples)):
+            raise ValueError(f"t_rand must be [{origins.shape[0]}, {int(num_samples)}]")
+    if use_occupancy and not grid.occupancy_current():
+        grid.build_occupancy()
+    batch = RayBatch(origins, directions, int(num_samples), float(np.float32(near)), float(np.float32(far)), t_rand=t_rand)
+    first, _ = grid.kernel_tensors()
+    return _DistortionLoss.apply(first, grid, batch, render_flags(False, False, optimized_sampling, use_occupancy))
 
 
 def prune_grid_raw(grid: VoxelGrid, max_weight: Tensor, threshold: float, dilate: int, fill_density: float, keep: Optional[Tensor] = None,

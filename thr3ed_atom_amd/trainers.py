@@ -54,7 +54,7 @@ from .ops import (
 )
 from .optim import ExponentialLR, FlatGrid, FusedAdam
 from .render_interface import Rays
-from .renderers import _check_supported, render_sh_voxel_grid
+from .renderers import _check_supported, render_sh_voxel_grid, render_sh_voxel_grid_pair
 from .volumetric_model import VolumetricModel
 from .voxels import VoxelGrid, scale_voxel_grid_with_required_output_size
 
@@ -133,14 +133,18 @@ class StepStats:
     the ring (one small launch) for code that keeps a history of StepStats objects.
     ``tv_density`` / ``tv_features``: the total-variation values of the grid the step's regulariser saw (TrainStepper(tv_*_weight=...)),
     read the same lazy way from the two sums rf_tv_grad wrote (``tv`` = (sums [2] in a ring slot, nodes N, features F, ring)); None
-    when TV is off."""
+    when TV is off.
+    ``distortion``: the sum over this rank's rays of the distortion loss l_r of the specular render's weights
+    (TrainStepper(distortion_weight=...)), summed when READ from the per-ray values rf_distortion left in a ring slot
+    (``distortion`` = (per-ray values [n], ring)); None when the weight is 0."""
 
     def __init__(self, specular_loss=None, diffuse_loss=None, specular_mse=None, diffuse_mse=None, sums: Optional[Tensor] = None, count: float = 1.0,
-                 has_diffuse: bool = True, ring=None, tv=None):
+                 has_diffuse: bool = True, ring=None, tv=None, distortion=None):
         self._values = (specular_loss, diffuse_loss, specular_mse, diffuse_mse)
         self._sums, self._count, self._has_diffuse = sums, float(count), has_diffuse
         self._ring = ring  # (executor dict holding "serial", serial of the producing step) or None
         self._tv = tv
+        self._distortion = distortion
 
     def _live_sums(self) -> Tensor:
         if self._ring is not None:
@@ -157,7 +161,20 @@ class StepStats:
             self._ring = None
         if self._tv is not None and self._tv[3] is not None:
             self._tv = (self._live_tv().clone(),) + self._tv[1:3] + (None,)
+        if self._distortion is not None and self._distortion[1] is not None:
+            self._distortion = (self._live_distortion().clone(), None)
         return self
+
+    def _live_distortion(self) -> Tensor:
+        per_ray, ring = self._distortion
+        if ring is not None and ring[0]["serial"] - ring[1] >= LOSS_RING:
+            raise RuntimeError(f"this StepStats was produced {ring[0]['serial'] - ring[1]} iterations ago: its slot of the distortion ring ({LOSS_RING} "
+                               "iterations) has been re-used -- read it earlier or keep StepStats.materialize() of it")
+        return per_ray
+
+    @property
+    def distortion(self):
+        return None if self._distortion is None else self._live_distortion().sum()
 
     def _live_tv(self) -> Tensor:
         sums, _, _, ring = self._tv
@@ -262,8 +279,18 @@ class TrainStepper:
         tv_density_weight: float = 0.0,
         tv_feature_weight: float = 0.0,
         tv_epsilon: float = 1e-8,
+        distortion_weight: float = 0.0,
     ):
-        """``tv_density_weight`` / ``tv_feature_weight`` (lambda_D, lambda_F >= 0): total-variation regularisation of the raw grid
+        """``distortion_weight`` (lambda >= 0): distortion-loss regularisation of the rendered rays (mip-NeRF 360; ops.distortion_loss),
+        ``loss += lambda * mean over the rays of the global batch of l_r``, on the samples and weights of the SPECULAR render: one launch
+        of rf_distortion per iteration with that render's rays, jitter (table or key and first_ray) and flags adds its density gradient to
+        the gradient bucket after the render gradients and before the data-parallel exchange and Adam -- so, like TV, the step keeps
+        the bucket (``fuse_optimizer`` resolves to False, the FlatGrid is not deferred, ``exchange`` resolves to "dense"; an explicit
+        fuse_optimizer=True or exchange="owner" raises).  Unlike TV it is a mean over rays: every rank scales by 1 / (its own rays) and
+        the exchange averages the ranks.  No gradient goes to rays or poses.  With weight 0 (default) nothing changes: nothing is
+        allocated or launched and every option resolves as without the argument.
+
+        ``tv_density_weight`` / ``tv_feature_weight`` (lambda_D, lambda_F >= 0): total-variation regularisation of the raw grid
         parameters, ``loss += lambda_D * TV_density + lambda_F * TV_features`` (ops.total_variation; ``tv_epsilon`` inside the square
         root).  One launch of rf_tv_grad per iteration adds its gradient to the gradient bucket after the render gradients and before
         the data-parallel exchange and Adam -- so a step with TV keeps the bucket: ``fuse_optimizer`` resolves to False, the FlatGrid is
@@ -299,6 +326,18 @@ class TrainStepper:
             raise ValueError("exchange='owner' exchanges gradient records and applies Adam inside the owners' brick flush, where no gradient tensor exists "
                              "for the total-variation gradient to be added to: a step with a TV weight needs exchange='dense' (the default with TV)")
         self._tv_ring = None
+        self.distortion_weight = float(distortion_weight)
+        if not (np.isfinite(self.distortion_weight) and self.distortion_weight >= 0.0):
+            raise ValueError("distortion_weight must be finite and non-negative")
+        self.distortion = self.distortion_weight > 0.0
+        if self.distortion and fuse_optimizer:
+            raise ValueError("fuse_optimizer=True applies Adam inside the brick flush, where no gradient tensor exists in memory for the distortion-loss "
+                             "gradient to be added to: a step with a distortion weight needs fuse_optimizer=False (the default with it)")
+        if self.distortion and exchange == "owner":
+            raise ValueError("exchange='owner' exchanges gradient records and applies Adam inside the owners' brick flush, where no gradient tensor exists "
+                             "for the distortion-loss gradient to be added to: a step with a distortion weight needs exchange='dense' (the default with it)")
+        self._distortion_ring = None
+        self.keeps_bucket = self.tv or self.distortion  # a regulariser adds to the gradient in HBM ahead of Adam
         self.ray_selection = ray_selection
         # fused=True runs the iteration as a fixed sequence of launches (forward, loss+gradient, backward per
         # render, then Adam which also clears the gradient bucket) without building an autograd graph;
@@ -338,7 +377,7 @@ class TrainStepper:
         self.data_parallel = data_parallel
         # autograd steps (fused=False) on a grid in the reference's own tensors: the backward passes leave record lists and the
         # optimizer sums them in one merged brick pass with Adam in its flush (optim.FlatGrid(deferred=True))
-        self.flat = FlatGrid(grid, deferred=not self.fused and not (self.data_parallel and rfdist._collectives_on()) and not self.tv)
+        self.flat = FlatGrid(grid, deferred=not self.fused and not (self.data_parallel and rfdist._collectives_on()) and not self.keeps_bucket)
         self.optimizer = FusedAdam(self.flat, lr=learning_rate, betas=(0.9, 0.999))
         if backward == "auto":
             # binned from 256 bricks of 8^3 nodes on: the brick pass has one workgroup per brick, and on the first grids of a progressive
@@ -368,7 +407,7 @@ class TrainStepper:
         for d in grid.grid_dims:
             padded_nodes *= (d + 7) // 8 * 8
         fits_flush = padded_nodes * max(4, grid.num_features - 3) < (1 << 31)
-        can_fuse = self.merged_bricks and single and grid.storage != "reference" and (grid.num_features + 1) % 4 == 0 and fits_flush and not self.tv
+        can_fuse = self.merged_bricks and single and grid.storage != "reference" and (grid.num_features + 1) % 4 == 0 and fits_flush and not self.keeps_bucket
         # exchange (data parallel; the reference has none: modules/trainers.py:338-341 is one device's backward + step):
         #   "owner": OWNER-COMPUTES.  Every rank owns an equal range of x-slabs of bricks.  The ranks exchange their gradient RECORDS
         #     (48 / 32 B each, already sorted by brick, so what an owner needs of a rank's list is ONE slice) instead of the dense
@@ -379,7 +418,7 @@ class TrainStepper:
         if exchange not in ("auto", "owner", "dense"):
             raise ValueError("exchange must be 'auto', 'owner' or 'dense'")
         world = rfdist.world_size()
-        can_owner = (not self.tv and not single and can_merge and merge_bricks is not False and fuse_optimizer is not False and grid.storage != "reference"
+        can_owner = (not self.keeps_bucket and not single and can_merge and merge_bricks is not False and fuse_optimizer is not False and grid.storage != "reference"
                      and (grid.num_features + 1) % 4 == 0 and fits_flush and world <= (8 if grid.num_features > 3 else 4) and self.brick_size == 8
                      and grid.grid_dims[0] % (8 * world) == 0)  # (a degree-0 grid's 2 W lists are all of ONE kind: at most 8 per brick pass)
         if exchange == "owner" and not can_owner:
@@ -475,13 +514,27 @@ class TrainStepper:
         # (The diffuse render, its loss and its adjoint on a side stream -- so that the two forward kernels and the two adjoints share
         # the machine like the fused step's paired launches -- measured no gain: 0.822 against 0.812 ms per iteration; each kernel
         # fills the machine by itself.  docs/experiments.md D.)
-        if self.diffuse and ops.PAIR_RENDERS:
+        dist_jitter = None
+        if self.distortion:
+            # the specular render's jitter is drawn HERE (the draw render_sh_voxel_grid would make, at the same place of the RNG
+            # stream) and handed to the render, so that the distortion launch below sees the samples that render used
+            cfg_now = vol_mod.render_config
+            if cfg_now.perturb_sampled_points:
+                kind = getattr(cfg_now, "jitter", "keyed")
+                if kind not in ("keyed", "torch"):
+                    raise ValueError("SHVoxGridRenderConfig.jitter must be 'keyed' or 'torch'")
+                n_rays, S_now = rays.origins.shape[0], int(cfg_now.num_samples_per_ray)
+                dist_jitter = ops.KeyedJitter(ops.draw_jitter_key(), 0) if kind == "keyed" else torch.rand(n_rays, S_now, dtype=torch.float32, device=rays.origins.device)
+        if self.distortion and self.diffuse and ops.PAIR_RENDERS:
+            spec_out, diff_out = render_sh_voxel_grid_pair(grid, rays, vol_mod.render_config, t_rands=(dist_jitter, None))
+            total, spec_loss, spec_mse, diff_loss, diff_mse = ops.l1_loss_pair_with_mse(spec_out.colour, diff_out.colour, pixels)
+        elif self.diffuse and ops.PAIR_RENDERS:
             # both renders as ONE autograd node and both loss lines as one (VolumetricModel.render_rays_pair, ops.l1_loss_pair_with_mse):
             # the launches of the fused step's pairs -- one forward, one loss, [backward:] one offsets, one emit -- under autograd
             spec_out, diff_out = vol_mod.render_rays_pair(rays)
             total, spec_loss, spec_mse, diff_loss, diff_mse = ops.l1_loss_pair_with_mse(spec_out.colour, diff_out.colour, pixels)
         else:
-            spec = vol_mod.render_rays(rays).colour
+            spec = (render_sh_voxel_grid(grid, rays, vol_mod.render_config, t_rand=dist_jitter) if self.distortion else vol_mod.render_rays(rays)).colour
             total, spec_mse = ops.l1_loss_with_mse(spec, pixels)
             spec_loss, diff_loss, diff_mse = total.detach(), None, None
             if self.diffuse:
@@ -490,6 +543,10 @@ class TrainStepper:
                 total = total + dl
                 diff_loss = dl.detach()
         total.backward(self._unit_gradient(total))
+        dist = None
+        if self.distortion:
+            dist = self._add_distortion_gradient(rays.origins, rays.directions, dist_jitter,
+                                                 render_flags(cfg.white_bkgd, False, cfg.optimized_sampling, cfg.use_occupancy_mask))
         tv = self._add_tv_gradient()
         if self.data_parallel:
             rfdist.all_reduce_mean_(self.flat.flat_grad)
@@ -497,7 +554,7 @@ class TrainStepper:
         if not self.flat.deferred:  # (the deferred step re-laid the Parameters out and marked shadow and mask state itself)
             grid.invalidate_occupancy()
         self._grad_clean = False
-        return StepStats(spec_loss, diff_loss, spec_mse, diff_mse, tv=tv)
+        return StepStats(spec_loss, diff_loss, spec_mse, diff_mse, tv=tv, distortion=dist)
 
     def _add_tv_gradient(self):
         """Total variation on: ONE launch of rf_tv_grad adds lambda_D dTV_density + lambda_F dTV_features to the gradient bucket -- after
@@ -517,6 +574,31 @@ class TrainStepper:
         sums = ring["sums"][slot]
         ops.tv_grad_raw(grid, self.tv_density_weight, self.tv_feature_weight, gd, gf, sums, self.tv_epsilon)
         return (sums, float(np.prod(grid.grid_dims)), float(grid.num_features), (ring, ring["serial"]))
+
+    def _add_distortion_gradient(self, origins: Tensor, directions: Tensor, jitter, flags: int):
+        """Distortion loss on: ONE launch of rf_distortion on the specular render's samples -- its rays, its jitter (a [n, S] table, a
+        KeyedJitter with the render's key and first_ray, or None) and its flags -- adds lambda / n * sum_r d l_r / d D to the density part
+        of the gradient bucket, after the render gradients and before the exchange and Adam (whose mean over equally sized ranks makes
+        it the mean over the global batch; the bucket paths carry no other loss scale), and leaves the per-ray values of the iteration in the
+        next slot of a ring.  Returns StepStats' ``distortion`` argument; None when the weight is 0."""
+        if not self.distortion:
+            return None
+        grid, cfg = self.vol_mod.thre3d_repr, self.vol_mod.render_config
+        origins = origins.detach().to(torch.float32).contiguous()
+        directions = directions.detach().to(torch.float32).contiguous()
+        n = origins.shape[0]
+        gd, _ = self.flat.views_for_accumulation()
+        ring = self._distortion_ring
+        if ring is None or ring["per_ray"].device != gd.device or ring["per_ray"].shape[1] != n:
+            ring = self._distortion_ring = {"per_ray": torch.zeros((LOSS_RING, n), dtype=torch.float32, device=gd.device), "slot": 0, "serial": 0}
+        slot, ring["slot"] = ring["slot"], (ring["slot"] + 1) % LOSS_RING
+        ring["serial"] += 1
+        per_ray = ring["per_ray"][slot]  # (overwritten by the launch)
+        if n > 0:
+            batch = ops.RayBatch(origins, directions, int(cfg.num_samples_per_ray), float(np.float32(cfg.camera_bounds.near)),
+                                 float(np.float32(cfg.camera_bounds.far)), t_rand=jitter)
+            ops.distortion_raw(grid, batch, int(flags) & ~_lib.FLAG_RENDER_DIFFUSE, self.distortion_weight / n, None, per_ray, gd)
+        return (per_ray, (ring, ring["serial"]))
 
     def _draw_jitter(self, cfg, n: int, S: int, device, given, i: int, first_ray: int = 0):
         if given is not None:
@@ -612,17 +694,20 @@ class TrainStepper:
         with ops._span("train_step", dev):
             rc = _lib.load().rf_train_step(C.byref(rf_grid), C.byref(st), torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(rc, "rf_train_step")
-        del keep, jit
-        tv = None
+        tv = dist = None
         if self.fuse_optimizer:
             self._grad_clean = True  # the bucket is not used at all
         else:
+            if self.distortion:  # (the call drew the batch into the executor's ray buffers when it selected it itself)
+                ro, rd = (ex["origins"], ex["directions"]) if selection is not None else (origins, directions)
+                dist = self._add_distortion_gradient(ro, rd, jit[0], flags)
             tv = self._add_tv_gradient()
             if self.data_parallel and rfdist._collectives_on():
                 rfdist.all_reduce_mean_(self.flat.flat_grad)
             opt.step()
             self._grad_clean = False
-        return StepStats(sums=sums, count=3 * n, ring=(ex, serial), tv=tv)
+        del keep, jit
+        return StepStats(sums=sums, count=3 * n, ring=(ex, serial), tv=tv, distortion=dist)
 
     def _owner_state(self, ex, device):
         """Persistent state of the owner-computes exchange: who owns which x-slabs of bricks, the ranks' offset tables, where every
@@ -921,7 +1006,7 @@ class TrainStepper:
                                             b["cursor"], b["sorted"], hist_clear=b["hist"])
             lists.append((b["sorted"], offsets, diffuse))
         opt = self.optimizer
-        tv = None
+        tv = dist = None
         if self.fuse_optimizer:
             opt.step_count += 1
             nd = self.flat.flat_gradient_parts()[0].numel()
@@ -933,13 +1018,14 @@ class TrainStepper:
         else:
             gd, gf = self.flat.views_for_accumulation()
             brick_accumulate_raw(grid, self.brick_size, lists, gd, gf, accumulate=False)  # overwrites the whole bucket
+            dist = self._add_distortion_gradient(origins, directions, passes[0][1], passes[0][2])
             tv = self._add_tv_gradient()
             if self.data_parallel and rfdist._collectives_on():
                 rfdist.all_reduce_mean_(self.flat.flat_grad)
             opt.step()
             self._grad_clean = False
         means = sums / float(3 * n)
-        return StepStats(means[0], means[2], means[1], means[3], tv=tv)
+        return StepStats(means[0], means[2], means[1], means[3], tv=tv, distortion=dist)
 
     def _fused_step_on(self, rays: Rays, pixels: Tensor, t_rand_given=None) -> StepStats:
         vol_mod, grid = self.vol_mod, self.vol_mod.thre3d_repr
@@ -960,8 +1046,8 @@ class TrainStepper:
         # data parallel: with split storage the diffuse pass only touches `base`, so the all-reduce of the `rest`
         # gradients (201 of the 235 MB at degree 2) starts right after the specular backward and overlaps it
         dp = self.data_parallel and rfdist._collectives_on()
-        # (with total variation the exchange waits for the whole gradient: the TV launch adds to both tensors after the last render)
-        overlap = dp and self.diffuse and grid.storage != "reference" and gf is not None and not self.tv
+        # (with total variation or the distortion loss the exchange waits for the whole gradient: their launches add to the tensors after the last render)
+        overlap = dp and self.diffuse and grid.storage != "reference" and gf is not None and not self.keeps_bucket
         # ... and with equal chunks the exchange is split around a sharded Adam (reduce-scatter | update 1/N | all-gather)
         sharded = overlap and self.shard_optimizer and rfdist.can_shard(gd.numel()) and rfdist.can_shard(gf.numel())
         reduce_async = rfdist.reduce_scatter_mean_async if sharded else rfdist.all_reduce_mean_async
@@ -1000,9 +1086,12 @@ class TrainStepper:
                 brick_accumulate_raw(grid, self.brick_size, [(bins["sorted"], offsets, diffuse)], gd, gf, accumulate=diffuse)
             else:
                 render_backward_raw(grid, origins, directions, t_rand, S, near, far, flags, caches, g_colour, None, None, gd, gf)
+            if i == 0:
+                specular_pass = (t_rand, flags)
             if overlap and i == 0:
                 pending.append(reduce_async(self.flat.flat_gradient_parts()[1]))
         self._grad_clean = False
+        dist = self._add_distortion_gradient(origins, directions, *specular_pass)
         tv = self._add_tv_gradient()
         if overlap:
             pending.append(reduce_async(self.flat.flat_gradient_parts()[0]))
@@ -1023,7 +1112,7 @@ class TrainStepper:
             self.optimizer.step()
         self._grad_clean = False
         means = sums / float(3 * n)
-        return StepStats(means[0], means[2] if self.diffuse else None, means[1], means[3] if self.diffuse else None, tv=tv)
+        return StepStats(means[0], means[2] if self.diffuse else None, means[1], means[3] if self.diffuse else None, tv=tv, distortion=dist)
 
     def _bin_buffers(self, n: int, S: int, device):
         b = self._bins
@@ -1101,6 +1190,7 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     tv_density_weight: float = 0.0,
     tv_feature_weight: float = 0.0,
     tv_epsilon: float = 1e-8,
+    distortion_weight: float = 0.0,
     prune_threshold: Optional[float] = None,
     prune_dilate: int = 1,
 ) -> VolumetricModel:
@@ -1113,6 +1203,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     ranks equally).
     ``tv_density_weight`` / ``tv_feature_weight`` / ``tv_epsilon``: total-variation regularisation of the grid in every stage
     (TrainStepper); the summary lines then carry ``tv_density`` / ``tv_features``.
+    ``distortion_weight``: distortion-loss regularisation of the specular render's rays in every stage (TrainStepper); the summary
+    lines then carry ``distortion``, the mean of the per-ray values over this rank's batch.
     ``prune_threshold`` (None = off: nothing is launched or allocated) / ``prune_dilate``: at the end of every stage -- before the
     grid is upsampled, and once after the last stage -- the nodes whose largest compositing weight over the stage's training views
     stays at or below the threshold are emptied (pruning.node_max_weights + prune_voxel_grid); ``history`` gets a row with the
@@ -1159,7 +1251,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
         batches = data.image_batches(image_batch_cache_size)
         lr = learning_rate * (stagewise_lr_decay_gamma ** (stage - 1))
         stepper = TrainStepper(vol_mod, ray_batch_size, lr, apply_diffuse_render_regularization, ray_selection=ray_selection, global_batch=global_batch,
-                               tv_density_weight=tv_density_weight, tv_feature_weight=tv_feature_weight, tv_epsilon=tv_epsilon)
+                               tv_density_weight=tv_density_weight, tv_feature_weight=tv_feature_weight, tv_epsilon=tv_epsilon,
+                               distortion_weight=distortion_weight)
         scheduler = ExponentialLR(stepper.optimizer, lr_decay_gamma_per_stage)
         if is_main:
             log(
@@ -1179,6 +1272,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 row.update(stats.psnr())
                 if stats.tv_density is not None:
                     row["tv_density"], row["tv_features"] = float(stats.tv_density), float(stats.tv_features)
+                if stats.distortion is not None:
+                    row["distortion"] = float(stats.distortion) / max(stats._distortion[0].numel(), 1)
                 if history is not None:
                     history.append(row)
                 if is_main:
