@@ -451,6 +451,36 @@ int rf_node_max_weight(const RFGrid* grid, const RFRayBatch* rays, uint32_t flag
 int rf_prune_grid(const RFGrid* grid, const float* max_weight_dev, float threshold, int32_t dilate, float fill_density,
                   float* densities_dev, uint8_t* keep_dev, int64_t* counts_dev, void* stream);
 
+/* The content box of a field: node n PASSES iff its own activated density sigma_n = post(pre(D_n * density_scale)) > threshold
+ * (strict; the helpers of the render under grid->density_mode, no interpolation: a node's value, not a sample's).  The call MERGES
+ * into bounds_dev [6] (int32): bounds[a] = min(bounds[a], i_a) and bounds[3 + a] = max(bounds[3 + a], i_a) over the passing nodes
+ * (i_a = the node's index on axis a), and ADDS their number to count_dev[0] (int64, optional).  The caller initialises bounds to
+ * {X, Y, Z, -1, -1, -1}; a field without a passing node leaves all seven values untouched.  Several calls (several grids, or
+ * thresholds) accumulate.  One thread per node; a wave without a passing node does nothing, any other reduces its six values
+ * across the wave and issues six int32 atomic min / max and one 64-bit add: integer atomics, so the result does not depend on the
+ * order of arrival -- exact and reproducible.  Every layout, F and density mode; only the density element of a node is read
+ * (split / bricked: of its base record), never a feature, never a padding node of bricked storage.  Before any device access:
+ * RF_ERR_NULL_POINTER (grid, its tensors, bounds_dev), RF_ERR_BAD_SHAPE (dims, a NaN or negative threshold).  (Added to ABI
+ * version 4 compatibly: no existing struct or signature changed.) */
+int rf_node_bounds(const RFGrid* grid, float threshold, int32_t* bounds_dev, int64_t* count_dev, void* stream);
+
+/* A field moved into another box: crop, re-grid, refine.  scale / offset are HOST arrays of 3 floats.  Destination node
+ * (i_x, i_y, i_z) of `dst` sits, on axis a, at the continuous source index   s_a = fmaf(scale_a, (float)i_a, offset_a).
+ * If any s_a < -0.5 or s_a > n_a - 0.5 (n = src dims: nodes are voxel centres, so this is the source BOX) the node becomes
+ * (density fill_density, every feature 0).  Otherwise s_a is clamped to [0, n_a - 1], i0 = min(floor(s), n - 1),
+ * i1 = min(i0 + 1, n - 1), lambda = s - i0, and each of the F + 1 RAW channels (no density_scale, no activation: what a stage
+ * transition resamples) is the trilinear sum of the 8 corners in a FIXED order: corner k = dx * 4 + dy * 2 + dz ascending with
+ * weight w_k = (wx * wy) * wz (w = 1 - lambda for d = 0, lambda for d = 1), v = val_0 * w_0, then v = fmaf(val_k, w_k, v),
+ * k = 1 .. 7.  Consequences: scale 1 with an integer offset makes every weight exactly 1 or 0 -- a bit-exact copy of the source
+ * sub-volume for finite values (an exact crop); scale_a = n_src / n_dst with offset_a = 0.5 scale_a - 0.5 restates
+ * F.interpolate(trilinear, align_corners=False), though not bit for bit (rf_upsample_grid keeps that job).  Any layout on either
+ * side, same num_features, any dims >= 1; dst's tensors are overwritten (padding nodes of bricked storage are not touched), its
+ * AABB / activation fields are not used.  One thread per (destination node, channel), values landing in the destination's layout.
+ * Before any device access: RF_ERR_NULL_POINTER (grids, tensors, scale, offset), RF_ERR_BAD_SHAPE (dims, num_features mismatch, a
+ * non-finite or non-positive scale, a non-finite offset, a NaN fill, a destination tensor that IS a source tensor).  (Added to ABI
+ * version 4 compatibly: no existing struct or signature changed.) */
+int rf_resample_grid(const RFGrid* src, const RFGrid* dst, const float* scale, const float* offset, float fill_density, void* stream);
+
 /* Distortion loss of the rendered rays (mip-NeRF 360; DVGOv2's O(S) form): the regulariser that acts ALONG the ray and pulls its
  * compositing weights into one compact interval.  For every ray of the batch, with the samples i = 0 .. S-1 and the weights
  * w_i = T_i * alpha_i exactly as rf_render_forward computes them (same sampling, t_rand_dev / jitter key, first_ray / camera,

@@ -115,6 +115,9 @@ def load_datasets(config, dev):
               help="at the end of every stage, empty the nodes whose largest compositing weight over the training views stays at or below this (negative: off)")
 @click.option("--prune_dilate", type=click.INT, required=False, default=1, help="nodes within this many steps of a node above the threshold are kept")
 @click.option("--distortion_weight", type=click.FLOAT, required=False, default=0.0, help="weight of the distortion loss of the specular render's rays (0: off)")
+@click.option("--tighten_threshold", type=click.FLOAT, required=False, default=-1.0,
+              help="at the end of every stage but the last, tighten the box to the nodes whose activated density exceeds this and spend the next stage's nodes inside it (negative: off)")
+@click.option("--tighten_margin", type=click.IntRange(min=0), required=False, default=1, help="nodes kept around the content box when tightening")
 @click.option("--seed", type=click.INT, required=False, default=42, help="seed of torch's generators")
 # fmt: on
 # -------------------------------------------------------------------------------------
@@ -157,7 +160,8 @@ def main(**kwargs) -> None:
         summary_freq=config["summary_frequency"], apply_diffuse_render_regularization=config["apply_diffuse_render_regularization"],
         global_batch=config["global_batch"], tv_density_weight=config["tv_density_weight"], tv_feature_weight=config["tv_feature_weight"],
         tv_epsilon=config["tv_epsilon"], distortion_weight=config["distortion_weight"], prune_threshold=config["prune_threshold"] if config["prune_threshold"] >= 0.0 else None,
-        prune_dilate=config["prune_dilate"],
+        prune_dilate=config["prune_dilate"], tighten_threshold=config["tighten_threshold"] if config["tighten_threshold"] >= 0.0 else None,
+        tighten_margin=config["tighten_margin"],
     )
 
 

@@ -49,5 +49,6 @@ from .mesh import Mesh, extract_mesh, write_ply  # noqa: F401
 from .ops import distortion_loss, total_variation  # noqa: F401
 from .pose_refinement import pose_error, refine_camera_pose  # noqa: F401
 from .pruning import PruneStats, node_max_weights, prune_voxel_grid  # noqa: F401
+from .resampling import TightenStats, content_bounds, crop_voxel_grid, resample_voxel_grid, tighten_voxel_grid  # noqa: F401
 
 __version__ = "0.1.0"

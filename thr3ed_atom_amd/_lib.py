@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = [
     "rf_tv_grad",
     "rf_node_max_weight",
     "rf_prune_grid",
+    "rf_node_bounds",
+    "rf_resample_grid",
     "rf_distortion",
     "rf_l1_loss_grad",
     "rf_adam_step",
@@ -314,6 +316,8 @@ def load() -> C.CDLL:
     lib.rf_tv_grad.argtypes = [C.POINTER(RFGrid), f32, f32, f32, vp, vp, vp, vp]
     lib.rf_node_max_weight.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, vp, vp]
     lib.rf_prune_grid.argtypes = [C.POINTER(RFGrid), vp, f32, i32, f32, vp, vp, vp, vp]
+    lib.rf_node_bounds.argtypes = [C.POINTER(RFGrid), f32, vp, vp, vp]
+    lib.rf_resample_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), fp, fp, f32, vp]
     lib.rf_distortion.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, f32, vp, vp, vp, vp]
     lib.rf_build_occupancy.argtypes = [C.POINTER(RFGrid), f32, vp, vp]
     lib.rf_l1_loss_grad.argtypes = [vp, vp, i64, f32, vp, vp, vp]

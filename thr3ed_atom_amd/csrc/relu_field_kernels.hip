@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -4796,6 +4797,115 @@ __global__ __launch_bounds__(256) void prune_grid_kernel(GridArgs g, const float
   }
 }
 
+// rf_node_bounds: the index box of the nodes whose OWN activated density sigma_n = post(pre(D_n * rho)) exceeds the threshold (no
+// interpolation), merged into bounds[0..2] (min) / bounds[3..5] (max), and their number added to count[0].  One thread per node, z
+// fastest; only a node's density element is read (node_lin: padding nodes of bricked storage are never addressed).  A wave whose
+// ballot is empty does nothing; otherwise its six values are reduced with xor shuffles (lanes that do not pass carry the neutral
+// elements) and lane 0 issues six int32 atomicMin / atomicMax and one 64-bit add.  Integer atomics: the result does not depend on
+// the order of arrival.
+__global__ __launch_bounds__(256) void node_bounds_kernel(GridArgs g, float threshold, int* __restrict__ bounds,
+                                                          unsigned long long* __restrict__ count, long long nodes) {
+  const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+  bool pass = false;
+  if (n < nodes) {
+    const int z = (int)(n % g.Z), y = (int)((n / g.Z) % g.Y), x = (int)(n / ((long long)g.Z * g.Y));
+    float pre = g.dens[(long long)node_lin(g, x, y, z) * g.dstride] * g.rho;
+    if (g.mode == RF_DENSITY_ABS) pre = fabsf(pre);
+    pass = density_post(pre, g.mode) > threshold;
+    if (pass) {
+      lo[0] = hi[0] = x;
+      lo[1] = hi[1] = y;
+      lo[2] = hi[2] = z;
+    }
+  }
+  const unsigned long long ballot = __ballot(pass);
+  if (ballot == 0ull) return;  // (wave-uniform)
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = min(lo[a], __shfl_xor(lo[a], off, kWave));
+      hi[a] = max(hi[a], __shfl_xor(hi[a], off, kWave));
+    }
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      atomicMin(bounds + a, lo[a]);
+      atomicMax(bounds + 3 + a, hi[a]);
+    }
+    if (count) atomicAdd(count, (unsigned long long)__popcll(ballot));
+  }
+}
+
+// rf_resample_grid: the RAW [F+1]-channel volume of `src` seen from another lattice.  Destination node i on axis a sits at the
+// continuous source index s_a = fma(scale_a, i_a, offset_a); a node with some s_a outside [-0.5, n_a - 0.5] (the source BOX: nodes are
+// voxel centres) is (fill, 0 ...), any other takes the trilinear sum of the 8 corners of its cell with s_a clamped to [0, n_a - 1],
+// i0 = min(floor(s), n - 1), i1 = min(i0 + 1, n - 1), lambda = s - i0.  No density scale, no activation.  The thread shape of
+// upsample_grid_kernel: one thread per (destination node, channel), channel fastest, any storage on either side.
+// SUMMATION ORDER (fixed, part of the contract): corner k = dx * 4 + dy * 2 + dz ascending, weight (wx * wy) * wz,
+// v = val[0] * w[0], then v = fma(val[k], w[k], v) for k = 1 .. 7.  With scale 1 and an integer offset every weight is exactly 1 or 0:
+// a bit-exact copy of finite values.
+struct ResampleAxis {
+  int i0, i1;
+  float w0, w1;
+  bool outside;
+};
+__device__ __forceinline__ ResampleAxis resample_axis(int dst, int in_size, float scale, float offset) {
+  float s = fmaf(scale, (float)dst, offset);
+  ResampleAxis a;
+  a.outside = s < -0.5f || s > (float)in_size - 0.5f;
+  s = fminf(fmaxf(s, 0.0f), (float)(in_size - 1));
+  a.i0 = min((int)floorf(s), in_size - 1);
+  a.i1 = min(a.i0 + 1, in_size - 1);
+  const float lambda = s - (float)a.i0;
+  a.w0 = 1.0f - lambda;
+  a.w1 = lambda;
+  return a;
+}
+
+struct ResampleMap {
+  float scale[3], offset[3];
+};
+
+__global__ __launch_bounds__(256) void resample_grid_kernel(GridArgs src, GridArgs dst, ResampleMap m, float fill, float* dst_first,
+                                                            float* dst_second, long long total) {
+  const int C = dst.F + 1, K = dst.F / 3;
+  for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
+    const int ch = (int)(it % C);
+    long long node = it / C;
+    const int z = (int)(node % dst.Z);
+    node /= dst.Z;
+    const int y = (int)(node % dst.Y), x = (int)(node / dst.Y);
+    const ResampleAxis ax = resample_axis(x, src.X, m.scale[0], m.offset[0]), ay = resample_axis(y, src.Y, m.scale[1], m.offset[1]),
+                       az = resample_axis(z, src.Z, m.scale[2], m.offset[2]);
+    float v;
+    if (ax.outside || ay.outside || az.outside) {
+      v = ch == 0 ? fill : 0.0f;
+    } else {
+      auto at = [&](int xi, int yi, int zi) -> float {
+        bool first;
+        const long long off = channel_offset(src, node_lin(src, xi, yi, zi), ch, K, first);
+        return (first ? src.dens : src.feat)[off];
+      };
+      float val[8], wgt[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int dx = k >> 2, dy = (k >> 1) & 1, dz = k & 1;
+        val[k] = at(dx ? ax.i1 : ax.i0, dy ? ay.i1 : ay.i0, dz ? az.i1 : az.i0);
+        wgt[k] = ((dx ? ax.w1 : ax.w0) * (dy ? ay.w1 : ay.w0)) * (dz ? az.w1 : az.w0);
+      }
+      v = val[0] * wgt[0];
+#pragma unroll
+      for (int k = 1; k < 8; ++k) v = fmaf(val[k], wgt[k], v);
+    }
+    bool first;
+    const long long off = channel_offset(dst, node_lin(dst, x, y, z), ch, K, first);
+    (first ? dst_first : dst_second)[off] = v;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side of the C ABI
 // ---------------------------------------------------------------------------------------------
@@ -5884,6 +5994,45 @@ int rf_prune_grid(const RFGrid* grid, const float* max_weight_dev, float thresho
   const long long nodes = (long long)g.X * g.Y * g.Z;
   hipLaunchKernelGGL(prune_grid_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, max_weight_dev, threshold,
                      (int)dilate, fill_density, densities_dev, keep_dev, reinterpret_cast<unsigned long long*>(counts_dev), nodes);
+  return launch_status();
+}
+
+int rf_node_bounds(const RFGrid* grid, float threshold, int32_t* bounds_dev, int64_t* count_dev, void* stream) {
+  const int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  if (!bounds_dev) return RF_ERR_NULL_POINTER;
+  if (!(threshold >= 0.0f)) return RF_ERR_BAD_SHAPE;  // (NaN fails the comparison too)
+  const GridArgs g = to_args(grid);
+  const long long nodes = (long long)g.X * g.Y * g.Z;
+  hipLaunchKernelGGL(node_bounds_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, threshold, bounds_dev,
+                     reinterpret_cast<unsigned long long*>(count_dev), nodes);
+  return launch_status();
+}
+
+int rf_resample_grid(const RFGrid* src, const RFGrid* dst, const float* scale, const float* offset, float fill_density, void* stream) {
+  int rc = check_grid(src);
+  if (rc != RF_OK) return rc;
+  rc = check_grid(dst);
+  if (rc != RF_OK) return rc;
+  if (!scale || !offset) return RF_ERR_NULL_POINTER;
+  if (src->num_features != dst->num_features) return RF_ERR_BAD_SHAPE;
+  ResampleMap m;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(scale[a]) || !(scale[a] > 0.0f) || !std::isfinite(offset[a])) return RF_ERR_BAD_SHAPE;
+    m.scale[a] = scale[a];
+    m.offset[a] = offset[a];
+  }
+  if (fill_density != fill_density) return RF_ERR_BAD_SHAPE;
+  // the destination is written while the source is read: no tensor of one may be a tensor of the other
+  const float* s[2] = {src->densities_dev, src->features_dev};
+  const float* d[2] = {dst->densities_dev, dst->features_dev};
+  for (int i = 0; i < 2; ++i)
+    for (int j = 0; j < 2; ++j)
+      if (s[i] && s[i] == d[j]) return RF_ERR_BAD_SHAPE;
+  const GridArgs gs = to_args(src), gd = to_args(dst);
+  const long long total = (long long)gd.X * gd.Y * gd.Z * (gd.F + 1);
+  hipLaunchKernelGGL(resample_grid_kernel, dim3(grid_1d(total, 256, 256LL * 64)), dim3(256), 0, (hipStream_t)stream, gs, gd, m, fill_density,
+                     const_cast<float*>(dst->densities_dev), const_cast<float*>(dst->features_dev), total);
   return launch_status();
 }
 

@@ -1252,6 +1252,41 @@ def prune_grid_raw(grid: VoxelGrid, max_weight: Tensor, threshold: float, dilate
     _lib.check(rc, "rf_prune_grid")
 
 
+def node_bounds_raw(grid: VoxelGrid, threshold: float, bounds: Tensor, count: Optional[Tensor] = None) -> None:
+    """Enqueue rf_node_bounds (include/relu_field.h): merge the index box of the nodes whose own activated density exceeds
+    ``threshold`` into ``bounds`` (int32 [6] = (min x, y, z, max x, y, z), the caller initialises it to (X, Y, Z, -1, -1, -1)) and
+    add their number to ``count`` (optional int64 [1]).  No autograd."""
+    lib = _lib.load()
+    _require_hip(bounds, "bounds")
+    if bounds.dtype != torch.int32 or bounds.numel() != 6 or not bounds.is_contiguous():
+        raise ValueError("bounds must hold six int32")
+    if count is not None:
+        _require_hip(count, "count")
+        if count.dtype != torch.int64 or count.numel() < 1 or not count.is_contiguous():
+            raise ValueError("count must hold one int64")
+    first, _ = grid.kernel_tensors()
+    _require_hip(first, "grid tensor")
+    rf_grid = grid.to_rf_grid()  # (only a node's density element is read: no shadow needed)
+    with _span("node_bounds", first.device):
+        rc = lib.rf_node_bounds(C.byref(rf_grid), float(threshold), bounds.data_ptr(), _ptr(count), _stream(first.device))
+    _lib.check(rc, "rf_node_bounds")
+
+
+def resample_grid_raw(src: VoxelGrid, dst: VoxelGrid, scale, offset, fill_density: float = 0.0) -> None:
+    """Enqueue rf_resample_grid (include/relu_field.h): overwrite the tensors of ``dst`` with the raw channels of ``src`` at the
+    continuous source indices ``s_a = fma(scale_a, i_a, offset_a)`` of its nodes (trilinear; ``(fill_density, 0 ...)`` outside the
+    source box).  Any storage on either side; ``dst``'s box and activations are not used.  No autograd."""
+    lib = _lib.load()
+    first, _ = src.kernel_tensors()
+    _require_hip(first, "source grid tensor")
+    _require_hip(dst.kernel_tensors()[0], "destination grid tensor")
+    rf_src, rf_dst = src.to_rf_grid(), dst.to_rf_grid()
+    with _span("resample_grid", first.device):
+        rc = lib.rf_resample_grid(C.byref(rf_src), C.byref(rf_dst), _lib.float3(scale), _lib.float3(offset), float(fill_density), _stream(first.device))
+    _lib.check(rc, "rf_resample_grid")
+    dst.invalidate_occupancy()  # (raw-pointer write: what hangs on the destination's densities is stale)
+
+
 def render_flags(white_bkgd: bool, render_diffuse: bool, optimized_sampling: bool, use_occupancy: bool) -> int:
     flags = 0
     flags |= _lib.FLAG_WHITE_BKGD if white_bkgd else 0

@@ -1193,6 +1193,8 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     distortion_weight: float = 0.0,
     prune_threshold: Optional[float] = None,
     prune_dilate: int = 1,
+    tighten_threshold: Optional[float] = None,
+    tighten_margin: int = 1,
 ) -> VolumetricModel:
     """Same arguments (minus the feedback/visualisation ones) and same schedule as the reference's
     trainer.  Returns the trained model; ``history`` (if given) collects the logged scalars.
@@ -1208,7 +1210,13 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     ``prune_threshold`` (None = off: nothing is launched or allocated) / ``prune_dilate``: at the end of every stage -- before the
     grid is upsampled, and once after the last stage -- the nodes whose largest compositing weight over the stage's training views
     stays at or below the threshold are emptied (pruning.node_max_weights + prune_voxel_grid); ``history`` gets a row with the
-    counts.  The stepper and the optimizer state are rebuilt per stage anyway, so no moments need handling."""
+    counts.  The stepper and the optimizer state are rebuilt per stage anyway, so no moments need handling.
+    ``tighten_threshold`` (None = off: nothing is launched or allocated) / ``tighten_margin``: at the end of every stage but the
+    last -- after the optional pruning, in place of the plain up-scale -- the bounding box is tightened to the nodes whose own
+    activated density exceeds the threshold plus ``tighten_margin`` nodes, and the next stage's node budget
+    prod(stage_sizes[stage]) is spent inside that box (resampling.tighten_voxel_grid: DVGO's rule); ``history`` gets a row with the
+    old and new dims and boxes.  A field without such a node is up-scaled as usual.  Replicas of a process group hold identical
+    parameters, so every rank computes the same box: no communication."""
     grid = vol_mod.thre3d_repr
     assert isinstance(grid, VoxelGrid), f"cannot use a {type(grid)} with this TrainProcedure"
     assert vol_mod.render_procedure is render_sh_voxel_grid, "non SH-based VoxelGrids cannot be used with this TrainProcedure"
@@ -1304,10 +1312,27 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
             if is_main:
                 log(f"pruned {pruned.pruned} of {pruned.pruned + pruned.kept} nodes after stage {stage} (threshold {prune_threshold}, dilate {prune_dilate})")
         if stage != num_stages:
+            tightened = None
+            if tighten_threshold is not None:
+                from .resampling import tighten_voxel_grid
+
+                budget = int(np.prod([int(v) for v in stage_sizes[stage]]))
+                new_grid, tight = tighten_voxel_grid(vol_mod.thre3d_repr, tighten_threshold, tighten_margin, num_nodes=budget)
+                row = {"stage": stage, "tightened": tight.passing_nodes > 0, "passing_nodes": tight.passing_nodes, "old_dims": tight.old_dims,
+                       "new_dims": tight.new_dims, "old_aabb": tight.old_aabb, "new_aabb": tight.new_aabb}
+                if history is not None:
+                    history.append(row)
+                if tight.passing_nodes > 0:
+                    tightened = new_grid
+                    if is_main:
+                        log(f"tightened the box after stage {stage}: dims {tight.old_dims} -> {tight.new_dims}, aabb {tuple(tight.old_aabb)} -> {tuple(tight.new_aabb)} "
+                            f"({tight.passing_nodes} nodes above {tighten_threshold}, margin {tighten_margin})")
+                elif is_main:
+                    log(f"no node above {tighten_threshold} after stage {stage}: the box stays")
             with torch.no_grad():
-                vol_mod.thre3d_repr = scale_voxel_grid_with_required_output_size(
-                    vol_mod.thre3d_repr, stage_sizes[stage]
-                ).to(vol_mod.device)
+                if tightened is None:
+                    tightened = scale_voxel_grid_with_required_output_size(vol_mod.thre3d_repr, stage_sizes[stage])
+                vol_mod.thre3d_repr = tightened.to(vol_mod.device)
     save("model_final.pth")
     if vol_mod.thre3d_repr.storage != incoming_storage:
         # hand the grid back in the storage it came in (normally "reference"): there ``.densities`` / ``.features`` are
