@@ -157,7 +157,7 @@ int rf_abi_version(void);
 const char* rf_error_string(int code);
 /* sizeof() of the ABI structs as this library was compiled, so that a binding can verify its own mirrors before the first
  * call: which = 0 RFGrid, 1 RFRayBatch, 2 RFRenderOut, 3 RFRenderGrads, 4 RFBrickList, 5 RFAdamState, 6 RFCamera,
- * 7 RFRaySelection, 8 RFPassScratch, 9 RFTrainStep; -1 for any other value. */
+ * 7 RFRaySelection, 8 RFPassScratch, 9 RFTrainStep, 10 RFGeometryOut; -1 for any other value. */
 int rf_abi_struct_size(int which);
 
 /* cast_rays (rendering/volumetric/utils/misc.py:12-50) + flatten_rays (:53-57):
@@ -502,6 +502,34 @@ int rf_resample_grid(const RFGrid* src, const RFGrid* dst, const float* scale, c
  * the density tensor).  (Added to ABI version 4 compatibly: no existing struct or signature changed.) */
 int rf_distortion(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float scale, const float* grad_loss_dev, float* loss_dev,
                   float* grad_first_dev, void* stream);
+
+/* Surface normals and quantile depth of the rendered rays: the geometry of a field seen from a camera.  For every ray of the batch,
+ * with the samples i = 0 .. S-1, their ray parameters z_i and the weights w_i = T_i * alpha_i exactly as rf_render_forward computes
+ * them (same sampling, t_rand_dev / jitter key, first_ray / camera, RF_FLAG_AABB_SAMPLING and RF_FLAG_OCCUPANCY_SKIP handling, last
+ * interval 1e10; w_i = 0 for samples outside the box):
+ *   acc_dev [N]             sum_i w_i -- the bits of RFRenderOut.acc_dev of the per-ray forward kernel
+ *   normal_dev [N,3]        sum_i w_i n_i in world space, NOT renormalised (its length is at most acc).  n_i = -g_i / |g_i|, and 0 where
+ *                           g_i = 0: g_i is the gradient with respect to the point of the trilinearly interpolated PRE-activation
+ *                           density (D * density_scale, |.| of it under RF_DENSITY_ABS; nodes outside the grid count as 0) at sample i,
+ *                           g_a = d pre / d idx_a * dims_a * norm_scale_a / 2.  The activation's slope is a positive scalar and does
+ *                           not enter; the sign convention is that of rf_mesh_emit's normals (out of the dense side).  A sample with
+ *                           w_i == 0 contributes nothing.
+ *   quantile_depth_dev [N]  z_i of the first sample with 1 - T_{i+1} >= quantile (the opacity accumulated through sample i; the same
+ *                           un-normalised ray parameter RFRenderOut.depth_dev sums), 0 if no sample reaches it.  quantile = 0.5: the
+ *                           median depth.
+ * Each output may be NULL (not all three).  One wave per ray, one result per ray, no atomics: bitwise reproducible.
+ * RF_FLAG_WHITE_BKGD / RF_FLAG_RENDER_DIFFUSE are accepted and change nothing; only the density element of a node is read (split /
+ * bricked: of its base record), never a feature.  Every density mode, layout, F and num_samples >= 1.  Zero rays: nothing is launched,
+ * RF_OK.  Before any device access: RF_ERR_NULL_POINTER (grid, its tensors, rays, their tensors, out, three NULL outputs,
+ * RF_FLAG_OCCUPANCY_SKIP without a mask), RF_ERR_BAD_SHAPE (dims, num_samples < 1, quantile outside (0, 1) or not finite),
+ * RF_ERR_UNSUPPORTED (num_features, density_mode).  (Added to ABI version 4 compatibly: no existing struct or signature changed;
+ * rf_abi_struct_size(10) is sizeof(RFGeometryOut).) */
+typedef struct RFGeometryOut {
+  float* normal_dev;          /* [N,3] sum_i w_i n_i, world space, NOT renormalised; may be NULL */
+  float* quantile_depth_dev;  /* [N]   see above; may be NULL                                     */
+  float* acc_dev;             /* [N]   sum_i w_i; may be NULL                                     */
+} RFGeometryOut;
+int rf_render_geometry(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float quantile, const RFGeometryOut* out, void* stream);
 
 /* Iso-surface extraction (csrc/mesh_kernels.hip; the contract -- field, lattice, Kuhn tetrahedra, edge keys, orientation and
  * canonical order -- is in that file's header and in DESIGN.md).  The level set sigma = iso_level of the grid's density on the

@@ -5,6 +5,7 @@ Checkpoints written by this build OR by the reference load (create_volumetric_mo
 names).  Video encoding (imageio) is out of scope: the colour frames are written as PNG files (PIL) or, without PIL, as .npy.
 
     python scripts/render_sh_based_voxel_grid.py -i out/saved_models/model_final.pth -o frames --num_frames 42
+    python scripts/render_sh_based_voxel_grid.py -i out/saved_models/model_final.pth -o frames --normals --median_depth
 """
 import os
 import sys
@@ -33,6 +34,9 @@ import thr3ed_atom_amd as rf  # noqa: E402
 # spiral path options
 @click.option("--vertical_camera_height", type=click.FLOAT, default=3.0, required=False, help="height at which the camera spiralling will happen")
 @click.option("--num_spiral_rounds", type=click.IntRange(min=1), default=2, required=False, help="number of rounds made while transitioning between spiral radii")
+# geometry outputs (one extra HIP pass per frame, shared by both flags)
+@click.option("--normals", is_flag=True, default=False, help="also write normal_XXXX.png: the composited surface normals, pixels of accumulated weight < 0.5 set to the background")
+@click.option("--median_depth", is_flag=True, default=False, help="also write median_depth_XXXX.npy: the depth at which each ray's opacity crosses one half (0 where it never does)")
 # Non-required video options:
 @click.option("--fps", type=click.IntRange(min=1), default=60, required=False, help="(video option of the reference: accepted, unused -- frames are written)")
 # fmt: on
@@ -61,6 +65,17 @@ def main(**kwargs) -> None:
             Image.fromarray(frame).save(os.path.join(config["output_path"], f"frame_{i:04d}.png"))
         else:
             np.save(os.path.join(config["output_path"], f"frame_{i:04d}.npy"), frame)
+        if config["normals"] or config["median_depth"]:
+            geo = model.render_geometry(pose, intr, num_samples_per_ray=config["overridden_num_samples_per_ray"])
+            if config["normals"]:
+                bkgd = (1.0, 1.0, 1.0) if getattr(model.render_config, "white_bkgd", False) else (0.0, 0.0, 0.0)
+                image = rf.normal_map_image(geo.extra[rf.constants.EXTRA_NORMALS], geo.extra[rf.constants.EXTRA_ACCUMULATED_WEIGHTS], bkgd)
+                if Image is not None:
+                    Image.fromarray(image).save(os.path.join(config["output_path"], f"normal_{i:04d}.png"))
+                else:
+                    np.save(os.path.join(config["output_path"], f"normal_{i:04d}.npy"), image)
+            if config["median_depth"]:
+                np.save(os.path.join(config["output_path"], f"median_depth_{i:04d}.npy"), geo.depth[..., 0].cpu().numpy())
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{len(poses)} frames of {intr.height}x{intr.width} x {config['overridden_num_samples_per_ray']} samples in {dt:.2f} s "

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = [
     "rf_node_bounds",
     "rf_resample_grid",
     "rf_distortion",
+    "rf_render_geometry",
     "rf_l1_loss_grad",
     "rf_adam_step",
     "rf_train_step",
@@ -221,6 +222,10 @@ class RFTrainStep(C.Structure):
     ]
 
 
+class RFGeometryOut(C.Structure):
+    _fields_ = [("normal_dev", C.c_void_p), ("quantile_depth_dev", C.c_void_p), ("acc_dev", C.c_void_p)]
+
+
 TRAIN_STEP_EVENTS = 11
 def train_step_pairing():
     """(forward renders paired, emit launches paired): rf_train_step runs both renders of an iteration -- and both adjoints -- in ONE
@@ -235,7 +240,7 @@ TRAIN_STEP_EVENT_NAMES = ["select_rays_and_pixels", "render_forward[spec,save]",
 
 
 # order of rf_abi_struct_size(which)
-ABI_STRUCTS = [RFGrid, RFRayBatch, RFRenderOut, RFRenderGrads, RFBrickList, RFAdamState, RFCamera, RFRaySelection, RFPassScratch, RFTrainStep]
+ABI_STRUCTS = [RFGrid, RFRayBatch, RFRenderOut, RFRenderGrads, RFBrickList, RFAdamState, RFCamera, RFRaySelection, RFPassScratch, RFTrainStep, RFGeometryOut]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -319,6 +324,7 @@ def load() -> C.CDLL:
     lib.rf_node_bounds.argtypes = [C.POINTER(RFGrid), f32, vp, vp, vp]
     lib.rf_resample_grid.argtypes = [C.POINTER(RFGrid), C.POINTER(RFGrid), fp, fp, f32, vp]
     lib.rf_distortion.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, f32, vp, vp, vp, vp]
+    lib.rf_render_geometry.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), u32, f32, C.POINTER(RFGeometryOut), vp]
     lib.rf_build_occupancy.argtypes = [C.POINTER(RFGrid), f32, vp, vp]
     lib.rf_l1_loss_grad.argtypes = [vp, vp, i64, f32, vp, vp, vp]
     lib.rf_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, i32, i32, vp]

@@ -15,6 +15,9 @@ INFINITY = 1e10
 # RenderOut.extra keys
 EXTRA_DISPARITY = "disparity"
 EXTRA_ACCUMULATED_WEIGHTS = "accumulated_weight"
+# ... of render_geometry (an extension of this build)
+EXTRA_NORMALS = "normals"
+EXTRA_QUANTILE_DEPTH = "quantile_depth"
 # ... the per-sample debug outputs of the accumulator (reference utils/constants.py:14-18, accumulate.py:96-107)
 EXTRA_POINT_DENSITIES = "point_densities"
 EXTRA_POINT_OCCUPANCIES = "point_occupancies"

@@ -427,6 +427,8 @@ __device__ __forceinline__ Corners corners_of(uint32_t packed, const float wts[6
 __device__ __forceinline__ float density_post(float pre, int mode);
 
 // density: post( interp( pre(D * rho) ) )  (voxels.py:292-309)
+// (interp_density_values, further down, is this function handing back the 8 corner values: a change here is a change there, or
+// rf_render_geometry's weights stop being the forward's bits)
 __device__ __forceinline__ float interp_density(const Corners& c, const GridArgs& g, float& pre_out) {
   float raw[8];
   if (g.near32) {  // (wave-uniform)
@@ -4758,6 +4760,132 @@ __global__ __launch_bounds__(kBlock) void distortion_kernel(GridArgs g, RayArgs 
   }
 }
 
+// =============================================================================================
+// rf_render_geometry: surface normals and quantile depth of the rendered rays.  The walk of
+// node_max_weight_kernel once more -- one wave per ray, lanes = the samples of a 64-sample chunk, the same helpers in the same order, so
+// w_i = alpha_i T_i is the forward's float bit for bit -- compositing three per-sample quantities:
+//   acc = sum_i w_i                    per-lane partial sums over the chunks, one wave sum at the end: render_forward_ray's order and bits
+//   N   = sum_i w_i n_i                n_i = -g_i / |g_i| (0 where g_i = 0), g_i the world-space gradient of the interpolated
+//                                      pre-activation density at the sample; per-lane products, a wave sum per chunk, a carry: no atomics
+//   z_q = z of the first sample with 1 - T_{i+1} >= quantile (0 if none): a ballot over the chunk and its first set lane
+// The gradient needs the 8 corner values themselves, not only their weighted sum: interp_density_values is interp_density (same
+// loads, same sum, same activation) handing them back.  No feature is read, nothing is written but one result per ray.
+// =============================================================================================
+__device__ __forceinline__ float interp_density_values(const Corners& c, const GridArgs& g, float v[8]) {
+  float raw[8];
+  if (g.near32) {  // (wave-uniform)
+    const unsigned int sb = (unsigned int)g.dstride * 4u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const unsigned int o = __umul24(c.lin[k], sb);
+      raw[k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(g.dens) + (size_t)o);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) raw[k] = g.dens[c.lin[k] * g.dstride];
+    asm volatile("" ::: "memory");  // (keeps the two branches' loads apart: merged, they lose the scalar-base addressing)
+  }
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    v[k] = raw[k] * g.rho;
+    if (g.mode == RF_DENSITY_ABS) v[k] = fabsf(v[k]);
+    acc = acc + v[k] * c.w[k];
+  }
+  if (g.mode == RF_DENSITY_RELU) return fmaxf(acc, 0.0f);
+  if (g.mode == RF_DENSITY_SOFTPLUS) return (acc > 20.0f) ? acc : log1pf(expf(acc));
+  return acc;
+}
+
+__global__ __launch_bounds__(kBlock) void render_geometry_kernel(GridArgs g, RayArgs r, uint32_t flags, float quantile, float* __restrict__ normal,
+                                                                 float* __restrict__ qdepth, float* __restrict__ acc_out) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
+  if (ray >= r.n) return;  // (wave-uniform)
+
+  const RayState st = load_ray(r, g, ray, flags);
+  const bool use_occ = (flags & RF_FLAG_OCCUPANCY_SKIP) && g.occ != nullptr;
+  const BoxSpan span = box_span(st, r, g);
+  // d idx_a / d p_a (locate): world gradient = index gradient * dims_a * norm_scale_a / 2
+  const float gscale[3] = {((float)g.X * g.nscale[0]) * 0.5f, ((float)g.Y * g.nscale[1]) * 0.5f, ((float)g.Z * g.nscale[2]) * 0.5f};
+  float T_carry = 1.0f, part_acc = 0.0f, zq = 0.0f;
+  float N[3] = {0.0f, 0.0f, 0.0f};
+  bool found = false;  // (wave-uniform)
+  const int nchunks = (r.S + kWave - 1) / kWave;
+  for (int chunk = 0; chunk < nchunks; ++chunk) {
+    if (chunk_outside_box(span, st, r, chunk)) continue;  // wave-uniform: sigma = 0 -> w = 0, T unchanged
+    const int s = chunk * kWave + lane;
+    const Sample sm = make_sample(st, r, g, ray, s);
+    bool live = sm.inside;
+    if (use_occ && live) live = cell_occupied(sm.cell, g);
+    float sigma = 0.0f;
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = 0.0f;
+    const uint32_t packed = pack_cell(sm.cell);
+    if (live) {
+      const float wts[6] = {sm.cell.w0[0], sm.cell.w1[0], sm.cell.w0[1], sm.cell.w1[1], sm.cell.w0[2], sm.cell.w1[2]};
+      const Corners cn = corners_of(packed, wts, g);
+      sigma = interp_density_values(cn, g, v);  // (reads element 0 of a node's density / base record only: no feature is touched)
+    }
+    float one_minus;
+    const float alpha = occupancy_alpha(sigma * sm.delta, one_minus);
+    float incl_e = sm.valid ? one_minus : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
+    wave_incl_scan_trans(incl_e, incl_a);
+    const float incl = prefix_transmittance(incl_e, incl_a);
+    const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
+    const float T = T_carry * excl;
+    const float wf = alpha * T;  // the forward's w (alpha = 0 where the sample is not live)
+    if (sm.valid) part_acc += wf;
+    const float w = live ? wf : 0.0f;
+
+    // quantile depth: C_i = 1 - T_{i+1}, T_{i+1} the transmittance the next sample is weighted with
+    if (!found) {
+      const float C = 1.0f - T_carry * incl;
+      const unsigned long long hit = __ballot(sm.valid && C >= quantile);
+      if (hit) {
+        found = true;
+        zq = read_lane(sm.z, __builtin_amdgcn_readfirstlane(__ffsll((long long)hit) - 1));
+      }
+    }
+    T_carry = T_carry * read_lane(incl, kWave - 1);
+
+    // index-space gradient of the trilinear interpolant: a corner outside the grid counts as 0 (corners_of masks its weight)
+    const int ix0 = (int)(packed & 0x7ffu) - 1, iy0 = (int)((packed >> 11) & 0x7ffu) - 1, iz0 = (int)(packed >> 22) - 1;
+    const bool okx[2] = {ix0 >= 0, ix0 + 1 < g.X}, oky[2] = {iy0 >= 0, iy0 + 1 < g.Y}, okz[2] = {iz0 >= 0, iz0 + 1 < g.Z};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] = (okx[k & 1] && oky[(k >> 1) & 1] && okz[k >> 2]) ? v[k] : 0.0f;
+    const float* w0 = sm.cell.w0;
+    const float* w1 = sm.cell.w1;
+    const float wyz[4] = {w0[1] * w0[2], w1[1] * w0[2], w0[1] * w1[2], w1[1] * w1[2]};  // [dy + 2 dz]
+    const float wxz[4] = {w0[0] * w0[2], w1[0] * w0[2], w0[0] * w1[2], w1[0] * w1[2]};  // [dx + 2 dz]
+    const float wxy[4] = {w0[0] * w0[1], w1[0] * w0[1], w0[0] * w1[1], w1[0] * w1[1]};  // [dx + 2 dy]
+    float gw[3];
+    gw[0] = (((v[1] - v[0]) * wyz[0] + (v[3] - v[2]) * wyz[1]) + ((v[5] - v[4]) * wyz[2] + (v[7] - v[6]) * wyz[3])) * gscale[0];
+    gw[1] = (((v[2] - v[0]) * wxz[0] + (v[3] - v[1]) * wxz[1]) + ((v[6] - v[4]) * wxz[2] + (v[7] - v[5]) * wxz[3])) * gscale[1];
+    gw[2] = (((v[4] - v[0]) * wxy[0] + (v[5] - v[1]) * wxy[1]) + ((v[6] - v[2]) * wxy[2] + (v[7] - v[3]) * wxy[3])) * gscale[2];
+    // n = -g / |g|, scaled by the largest component first (neither the squares of a huge gradient nor those of a tiny one leave float32)
+    const float big = fmaxf(fmaxf(fabsf(gw[0]), fabsf(gw[1])), fabsf(gw[2]));
+    float part[3] = {0.0f, 0.0f, 0.0f};
+    if (w != 0.0f && big > 0.0f) {  // a sample without weight contributes nothing, whatever its gradient
+      const float u[3] = {gw[0] / big, gw[1] / big, gw[2] / big};
+      const float len = sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) part[a] = w * -(u[a] / len);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) N[a] += wave_sum(part[a]);
+    if (T_carry == 0.0f) break;  // every later weight is exactly 0 (and 1 - T reached 1: the quantile is found)
+  }
+  const float acc = wave_sum(part_acc);
+  if (lane == 0) {
+    if (normal) normal[ray * 3 + 0] = N[0], normal[ray * 3 + 1] = N[1], normal[ray * 3 + 2] = N[2];
+    if (qdepth) qdepth[ray] = zq;
+    if (acc_out) acc_out[ray] = acc;
+  }
+}
+
 // rf_prune_grid: keep(n) = some node m of the grid with |m - n|_inf <= dilate has M[m] > threshold; a pruned node's raw density
 // is lowered to the fill.  GATHER form: one thread owns a node, reads the (2 dilate + 1)^3 neighbourhood of M (plain node order,
 // clipped to the grid) and writes only its own density element (node_lin: padding nodes of bricked storage are never addressed).
@@ -5117,6 +5245,7 @@ int rf_abi_struct_size(int which) {
     case 7: return (int)sizeof(RFRaySelection);
     case 8: return (int)sizeof(RFPassScratch);
     case 9: return (int)sizeof(RFTrainStep);
+    case 10: return (int)sizeof(RFGeometryOut);
     default: return -1;
   }
 }
@@ -5978,6 +6107,23 @@ int rf_distortion(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, fl
   else
     hipLaunchKernelGGL(distortion_kernel<false>, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, 0.0f, (const float*)nullptr, loss_dev,
                        (float*)nullptr);
+  return launch_status();
+}
+
+int rf_render_geometry(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float quantile, const RFGeometryOut* out, void* stream) {
+  int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  rc = check_rays(rays);
+  if (rc != RF_OK) return rc;
+  if (!out || (!out->normal_dev && !out->quantile_depth_dev && !out->acc_dev)) return RF_ERR_NULL_POINTER;
+  if (!(quantile > 0.0f && quantile < 1.0f)) return RF_ERR_BAD_SHAPE;  // (NaN fails the comparison too)
+  if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
+  if (rays->num_rays == 0) return RF_OK;
+  const GridArgs g = to_args(grid);
+  const RayArgs r = to_args(rays, flags);
+  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
+  hipLaunchKernelGGL(render_geometry_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, quantile, out->normal_dev,
+                     out->quantile_depth_dev, out->acc_dev);
   return launch_status();
 }
 

@@ -1229,6 +1229,119 @@ def distortion_loss(grid_or_model, rays, num_samples: int, bounds, *, perturb: b
     return _DistortionLoss.apply(first, grid, batch, render_flags(False, False, optimized_sampling, use_occupancy))
 
 
+def render_geometry_raw(grid: VoxelGrid, rays: RayBatch, flags: int, quantile: float = 0.5, normal: Optional[Tensor] = None,
+                        quantile_depth: Optional[Tensor] = None, acc: Optional[Tensor] = None) -> None:
+    """Enqueue rf_render_geometry (include/relu_field.h): with the samples and compositing weights w_i of ``rays`` as the forward
+    render with the same ``flags`` and jitter sees them, OVERWRITE ``normal`` [N, 3] with sum_i w_i n_i (world space, not
+    renormalised), ``quantile_depth`` [N] with the ray parameter of the first sample whose accumulated opacity reaches ``quantile``
+    (0 where none does) and ``acc`` [N] with sum_i w_i.  Each output is optional (not all three).  No autograd."""
+    lib = _lib.load()
+    first, _ = grid.kernel_tensors()
+    _require_hip(first, "grid tensor")
+    dev = first.device
+    rb, keep = _ray_batch_struct(rays, dev, "rf_render_geometry")
+    n = int(rb.num_rays)
+    for name, t, width in (("normal", normal, 3), ("quantile_depth", quantile_depth, 1), ("acc", acc, 1)):
+        if t is not None:
+            _require_hip(t, name)
+            if not (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n * width):
+                raise ValueError(f"rf_render_geometry: {name} must be a contiguous float32 tensor of {width} value(s) per ray ({n} rays)")
+    out = _lib.RFGeometryOut()
+    out.normal_dev, out.quantile_depth_dev, out.acc_dev = _ptr(normal), _ptr(quantile_depth), _ptr(acc)
+    use_occ = bool(int(flags) & _lib.FLAG_OCCUPANCY_SKIP)
+    rf_grid = grid.to_rf_grid(use_occupancy=use_occ)  # (only a node's density element is read: no shadow needed)
+    with _span("render_geometry", dev):
+        rc = lib.rf_render_geometry(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, rays.t_rand), float(quantile), C.byref(out), _stream(dev))
+    del keep
+    _lib.check(rc, "rf_render_geometry")
+
+
+def _geometry_render_out(grid: VoxelGrid, batches, total: int, flags: int, quantile: float):
+    """``batches``: (first row, RayBatch) pieces of ``total`` rays, one rf_render_geometry launch each into its rows of fresh buffers
+    -> RenderOut(None, quantile depth [total,1], {normals [total,3], accumulated weight [total,1]})"""
+    from .constants import EXTRA_ACCUMULATED_WEIGHTS, EXTRA_NORMALS
+    from .render_interface import RenderOut
+
+    dev = grid.kernel_tensors()[0].device
+    normal = torch.empty((total, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((total, 1), dtype=torch.float32, device=dev)
+    acc = torch.empty((total, 1), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for lo, batch, count in batches:
+            render_geometry_raw(grid, batch, flags, quantile, normal[lo : lo + count], depth[lo : lo + count], acc[lo : lo + count])
+    return RenderOut(colour=None, depth=depth, extra={EXTRA_NORMALS: normal, EXTRA_ACCUMULATED_WEIGHTS: acc})
+
+
+def _check_quantile(quantile) -> float:
+    q = float(quantile)
+    if not 0.0 < q < 1.0:  # (NaN fails too)
+        raise ValueError(f"quantile must lie in (0, 1), got {quantile!r}")
+    return q
+
+
+def render_geometry(grid_or_model, rays, num_samples: int, bounds, *, quantile: float = 0.5, perturb: bool = False, t_rand=None,
+                    jitter_key: Optional[int] = None, optimized_sampling: bool = False, use_occupancy_mask: bool = False):
+    """The geometry of a field as ``rays`` (a Rays-like object with flat ``origins`` / ``directions`` [N, 3]) see it, in one HIP launch
+    (include/relu_field.h: rf_render_geometry): a RenderOut with ``colour=None``,
+
+        depth                            [N, 1]  the QUANTILE depth: the ray parameter of the first sample at which the ray's accumulated
+                                                 opacity 1 - T reaches ``quantile`` (0.5: the median depth; 0 where it never does)
+        extra[EXTRA_NORMALS]             [N, 3]  sum_i w_i n_i, n_i = -grad(interpolated pre-activation density), normalised: world
+                                                 space, NOT renormalised (its length is at most the accumulated weight)
+        extra[EXTRA_ACCUMULATED_WEIGHTS] [N, 1]  sum_i w_i, the bits of a render's accumulated weight
+
+    with the samples and weights w_i of a render of ``num_samples`` samples between ``bounds`` (a CameraBounds or (near, far)).  The
+    jitter is chosen as in ``distortion_loss``: ``t_rand`` (a [N, S] tensor or a KeyedJitter), else ``jitter_key``, else with
+    ``perturb`` a freshly drawn key, else none.  ``grid_or_model``: a VoxelGrid on any storage, a VolumetricModel, or a module with the
+    reference VoxelGrid's attribute names.  Runs under no_grad: the outputs carry NO gradient, neither to the grid nor to the rays."""
+    quantile = _check_quantile(quantile)
+    grid = as_kernel_grid(getattr(grid_or_model, "thre3d_repr", grid_or_model))
+    near, far = (bounds.near, bounds.far) if hasattr(bounds, "near") else bounds
+    origins = rays.origins.detach().to(torch.float32).contiguous()
+    directions = rays.directions.detach().to(torch.float32).contiguous()
+    if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
+        raise AssertionError("render_geometry takes FLAT rays [N, 3]")
+    if t_rand is None:
+        if jitter_key is not None:
+            t_rand = KeyedJitter(int(jitter_key), 0)
+        elif perturb:
+            t_rand = KeyedJitter(draw_jitter_key(), 0)
+    elif not isinstance(t_rand, KeyedJitter):
+        t_rand = t_rand.detach().to(origins.device, torch.float32).contiguous()
+        if tuple(t_rand.shape) != (origins.shape[0], int(num_samples)):
+            raise ValueError(f"t_rand must be [{origins.shape[0]}, {int(num_samples)}]")
+    _require_hip(grid.kernel_tensors()[0], "grid tensor")
+    if use_occupancy_mask and not grid.occupancy_current():
+        grid.build_occupancy()
+    batch = RayBatch(origins, directions, int(num_samples), float(np.float32(near)), float(np.float32(far)), t_rand=t_rand)
+    return _geometry_render_out(grid, [(0, batch, origins.shape[0])], origins.shape[0], render_flags(False, False, optimized_sampling, use_occupancy_mask), quantile)
+
+
+def render_geometry_frame(grid, camera_intrinsics, camera_pose, render_config, quantile: float = 0.5, chunk_size: Optional[int] = None):
+    """``render_geometry`` for the pixels of a posed camera, flat [H W, .]: the rays are generated inside the kernel (RFCamera), the
+    frame goes in chunks of ``chunk_size`` pixels (None: one launch) addressed by ``first_ray`` -- no bit depends on the split.
+    Sampling, jitter and mask follow ``render_config`` (an SHVoxGridRenderConfig; the jitter is keyed, one key per frame)."""
+    quantile = _check_quantile(quantile)
+    grid = as_kernel_grid(grid)
+    _require_hip(grid.kernel_tensors()[0], "grid tensor")
+    height, width, focal = camera_intrinsics
+    total = int(height) * int(width)
+    use_occupancy = bool(getattr(render_config, "use_occupancy_mask", False))
+    if use_occupancy and not grid.occupancy_current():
+        grid.build_occupancy()
+    jitter = KeyedJitter(draw_jitter_key(), 0) if render_config.perturb_sampled_points else None
+    flags = render_flags(False, False, bool(render_config.optimized_sampling), use_occupancy)
+    bounds = render_config.camera_bounds
+    camera = (int(height), int(width), float(focal), camera_pose.rotation, camera_pose.translation)
+    chunk = total if not chunk_size else max(1, int(chunk_size))
+    batches = []
+    for lo in range(0, total, chunk):
+        count = min(chunk, total - lo)
+        batches.append((lo, RayBatch(None, None, int(render_config.num_samples_per_ray), float(np.float32(bounds.near)), float(np.float32(bounds.far)),
+                                     t_rand=jitter, camera=camera, first_ray=lo, num_rays=count), count))
+    return _geometry_render_out(grid, batches, total, flags, quantile)
+
+
 def prune_grid_raw(grid: VoxelGrid, max_weight: Tensor, threshold: float, dilate: int, fill_density: float, keep: Optional[Tensor] = None,
                    counts: Optional[Tensor] = None) -> None:
     """Enqueue rf_prune_grid on the grid's own density / base tensor, in place: nodes without a neighbour (Chebyshev distance

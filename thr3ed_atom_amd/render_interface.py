@@ -37,15 +37,16 @@ class Rays:
 
 @dataclasses.dataclass
 class RenderOut:
-    colour: Tensor  # [..., 3]
+    colour: Optional[Tensor]  # [..., 3]; None for a pass that renders no colour (render_geometry)
     depth: Tensor  # [..., 1]
     extra: Optional[Dict[str, Any]] = None
 
     def __post_init__(self):
-        if self.colour.shape[:-1] != self.depth.shape[:-1]:
-            raise AssertionError("colour and depth maps are shape-incompatible")
-        if self.colour.shape[-1] != NUM_COLOUR_CHANNELS:
-            raise AssertionError("only RGB colour maps are supported")
+        if self.colour is not None:
+            if self.colour.shape[:-1] != self.depth.shape[:-1]:
+                raise AssertionError("colour and depth maps are shape-incompatible")
+            if self.colour.shape[-1] != NUM_COLOUR_CHANNELS:
+                raise AssertionError("only RGB colour maps are supported")
         if self.depth.shape[-1] != 1:
             raise AssertionError("depth maps carry exactly one channel")
         if self.extra is None:
@@ -53,12 +54,12 @@ class RenderOut:
 
     def detach(self) -> "RenderOut":
         return RenderOut(
-            self.colour.detach(), self.depth.detach(), {k: v.detach() for k, v in self.extra.items()}
+            None if self.colour is None else self.colour.detach(), self.depth.detach(), {k: v.detach() for k, v in self.extra.items()}
         )
 
     def to(self, device) -> "RenderOut":
         return RenderOut(
-            self.colour.to(device), self.depth.to(device), {k: v.to(device) for k, v in self.extra.items()}
+            None if self.colour is None else self.colour.to(device), self.depth.to(device), {k: v.to(device) for k, v in self.extra.items()}
         )
 
 

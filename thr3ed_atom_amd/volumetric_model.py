@@ -174,6 +174,22 @@ class VolumetricModel:
                 out = out.to(torch.device("cpu"))
         return reshape_rendered_output(out, camera_intrinsics)
 
+    def render_geometry(self, camera_pose: CameraPose, camera_intrinsics: CameraIntrinsics, quantile: float = 0.5, **kwargs) -> RenderOut:
+        """The geometry of the field from a posed camera (``ops.render_geometry``; an extension of this build): a RenderOut with
+        ``colour=None``, ``depth`` [H, W, 1] = the quantile depth (0.5: median depth, 0 where the ray's opacity never reaches the
+        quantile) and ``extra`` = {EXTRA_NORMALS [H, W, 3] (sum of w_i n_i, world space, not renormalised), EXTRA_ACCUMULATED_WEIGHTS
+        [H, W, 1]}.  The rays are generated inside the kernel; the frame goes in chunks of the config's ``parallel_rays_chunk_size``
+        pixels, which changes no bit.  kwargs override render-config fields for this call (``num_samples_per_ray``,
+        ``optimized_sampling``, ``use_occupancy_mask``, ``perturb_sampled_points`` ...); the fields that only concern colour are not
+        used.  Under no_grad: the outputs carry no gradient."""
+        from .ops import render_geometry_frame
+
+        cfg = self._update_render_config(self._render_config, kwargs)
+        out = render_geometry_frame(self._thre3d_repr, camera_intrinsics, camera_pose, cfg, quantile, getattr(cfg, "parallel_rays_chunk_size", None))
+        height, width, _ = camera_intrinsics
+        shape = (int(height), int(width), -1)
+        return RenderOut(colour=None, depth=out.depth.reshape(*shape), extra={k: v.reshape(*shape) for k, v in out.extra.items()})
+
     @staticmethod
     def _gather_frame_shards(out: RenderOut, total_rays: int) -> RenderOut:
         """every rank's rows of a frame (``shard_range`` of its flat rays) -> the whole frame on every rank: ONE all-gather of the
