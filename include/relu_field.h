@@ -157,7 +157,7 @@ int rf_abi_version(void);
 const char* rf_error_string(int code);
 /* sizeof() of the ABI structs as this library was compiled, so that a binding can verify its own mirrors before the first
  * call: which = 0 RFGrid, 1 RFRayBatch, 2 RFRenderOut, 3 RFRenderGrads, 4 RFBrickList, 5 RFAdamState, 6 RFCamera,
- * 7 RFRaySelection, 8 RFPassScratch, 9 RFTrainStep, 10 RFGeometryOut; -1 for any other value. */
+ * 7 RFRaySelection, 8 RFPassScratch, 9 RFTrainStep, 10 RFGeometryOut, 11 RFImage; -1 for any other value. */
 int rf_abi_struct_size(int which);
 
 /* cast_rays (rendering/volumetric/utils/misc.py:12-50) + flatten_rays (:53-57):
@@ -548,6 +548,46 @@ int rf_mesh_count(const RFGrid* grid, int32_t subdivisions, float iso_level, int
 int rf_mesh_emit(const RFGrid* grid, int32_t subdivisions, float iso_level, const int64_t* offsets_dev, int64_t num_vertices,
                  int64_t num_faces, int64_t* edge_keys_dev, float* positions_dev, float* colours_dev, float* normals_dev,
                  int64_t* face_edges_dev, void* stream);
+
+/* ---- image metrics (csrc/image_kernels.hip) ------------------------------------------------------------------------------
+ * SSIM (Wang et al. 2004) of two float32 images of data range 1, per colour channel, and its adjoint -- the structural metric
+ * beside PSNR in held-out evaluation, and the D-SSIM term of full-frame losses (pose refinement).  The contract:
+ *   window   Gaussian, 11 x 11, sigma = 1.5, separable: g_k ~ exp(-(k - 5)^2 / (2 * 1.5^2)), normalised to sum 1;
+ *   moments  mu_x = G*x, mu_y = G*y, s_xx = G*x^2 - mu_x^2, s_yy = G*y^2 - mu_y^2, s_xy = G*xy - mu_x mu_y.  Variances are NOT
+ *            clamped (the form of pytorch-msssim and of 3DGS; jaxnerf's clamps are not applied);
+ *   S        = (A1 * A2) / (B1 * B2) with A1 = 2 mu_x mu_y + C1, A2 = 2 s_xy + C2, B1 = mu_x^2 + mu_y^2 + C1,
+ *            B2 = s_xx + s_yy + C2, C1 = 0.01^2, C2 = 0.03^2, in exactly this association: the SSIM of an image with itself is
+ *            exactly 1.0 in float32;
+ *   padding  RF_SSIM_VALID (what the NeRF literature's numbers use): only windows inside the image, map [H - 10, W - 10, C], H and
+ *            W at least 11.  RF_SSIM_SAME (the D-SSIM convention of 3DGS): the image zero-padded by 5, map [H, W, C], any H, W >= 1;
+ *   result   the mean of the map over pixels and channels.
+ * An image is addressed by ELEMENT strides (RFImage): a contiguous [H, W, C] tensor, a [C, H, W] tensor seen as [H, W, C], and a
+ * crop of a larger frame all go in without a copy, and all give the same bits for the same values.
+ *
+ * rf_ssim_tiles (host only): the number of workgroups of the forward launch = the length of partials_dev; a negative RF_ERR_* code
+ *   for shapes rf_ssim_forward refuses.
+ * rf_ssim_forward: two launches.  One workgroup per (16 x 32 map tile, channel) stages both images' tile and halo in LDS, filters
+ *   along the rows and then down the columns, and writes its float32 partial sum to partials_dev [rf_ssim_tiles]; one workgroup
+ *   then adds the partials in float64 and writes the mean to mean_dev [1].  Every sum has a fixed order and there are no atomics:
+ *   the result is bitwise reproducible.  Optional outputs, PLANAR: map_dev [C, Hm, Wm] (the map), dmaps_dev [3, C, Hm, Wm] (what the
+ *   adjoint reads: the total dS / d mu_x, dS / d s_xx, dS / d s_xy); NULL: not written.
+ * rf_ssim_backward: the gradient of the mean with respect to `image`, dL/dx_p = (g / N) [ (G*d_mu)_p + 2 x_p (G*d_sxx)_p +
+ *   y_p (G*d_sxy)_p ] (the derivative maps count as 0 outside the map's extent), gathered per pixel -- no atomics, reproducible --
+ *   and WRITTEN to grad_image (any strides of its own).  g = grad_mean_dev[0] is read by the kernel: no host synchronisation.
+ * Before any device access: RF_ERR_NULL_POINTER (an image struct, its data pointer, partials_dev / mean_dev, dmaps_dev /
+ * grad_mean_dev of the adjoint), RF_ERR_BAD_SHAPE (height, width or channels < 1, a zero stride, RF_SSIM_VALID below 11 x 11),
+ * RF_ERR_UNSUPPORTED (an unknown padding).  Every accepted shape holds at least one window: there is no zero-sized call.  (Added
+ * to ABI version 4 compatibly: no existing struct or signature changed; rf_abi_struct_size(11) is sizeof(RFImage).) */
+enum { RF_SSIM_VALID = 0, RF_SSIM_SAME = 1 };
+typedef struct RFImage {
+  float* data_dev;                      /* element (0, 0, 0)                               */
+  int64_t stride_h, stride_w, stride_c; /* floats between rows, columns, channels; non-zero */
+} RFImage;
+int64_t rf_ssim_tiles(int32_t height, int32_t width, int32_t channels, int32_t padding);
+int rf_ssim_forward(const RFImage* image, const RFImage* target, int32_t height, int32_t width, int32_t channels, int32_t padding,
+                    float* map_dev, float* dmaps_dev, float* partials_dev, float* mean_dev, void* stream);
+int rf_ssim_backward(const RFImage* image, const RFImage* target, int32_t height, int32_t width, int32_t channels, int32_t padding,
+                     const float* dmaps_dev, const float* grad_mean_dev, const RFImage* grad_image, void* stream);
 
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);

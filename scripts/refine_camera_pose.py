@@ -45,6 +45,7 @@ def _load_image(path: str) -> np.ndarray:
 @click.option("--rays_per_iteration", type=click.IntRange(min=1), default=None, required=False, help="random pixels per iteration (default: all)")
 @click.option("--num_samples_per_ray", type=click.IntRange(min=1), default=None, required=False, help="overridden num_samples_per_ray")
 @click.option("--seed", type=click.INT, default=0, required=False, help="seed of the pixel subsets")
+@click.option("--dssim_weight", type=click.FloatRange(0.0, 1.0), default=0.0, required=False, help="lambda of (1 - lambda) L1 + lambda (1 - SSIM) on the full frame (0: plain L1; needs all rays per iteration)")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -67,7 +68,7 @@ def main(**kwargs) -> None:
         render_kwargs["num_samples_per_ray"] = config["num_samples_per_ray"]
     pose, history = rf.refine_camera_pose(model, torch.from_numpy(image), intrinsics, pose0, num_iterations=config["num_iterations"],
                                           learning_rate=config["learning_rate"], rays_per_iteration=config["rays_per_iteration"],
-                                          seed=config["seed"], **render_kwargs)
+                                          seed=config["seed"], dssim_weight=config["dssim_weight"], **render_kwargs)
     os.makedirs(config["output_path"], exist_ok=True)
     c2w = np.concatenate([pose.rotation.cpu().numpy(), pose.translation.cpu().numpy()], axis=1).astype(np.float32)
     np.save(os.path.join(config["output_path"], "refined_pose.npy"), c2w)
@@ -83,7 +84,8 @@ def main(**kwargs) -> None:
         Image.fromarray(frame).save(os.path.join(config["output_path"], "refined_render.png"))
     except ImportError:
         np.save(os.path.join(config["output_path"], "refined_render.npy"), frame)
-    print(f"L1 {history[0]['loss']:.5f} -> {history[-1]['loss']:.5f} after {len(history)} iterations; pose written to {config['output_path']}")
+    label = "L1" if config["dssim_weight"] == 0.0 else "(1 - w) L1 + w (1 - SSIM)"
+    print(f"{label} {history[0]['loss']:.5f} -> {history[-1]['loss']:.5f} after {len(history)} iterations; pose written to {config['output_path']}")
 
 
 if __name__ == "__main__":

@@ -118,6 +118,7 @@ def load_datasets(config, dev):
 @click.option("--tighten_threshold", type=click.FLOAT, required=False, default=-1.0,
               help="at the end of every stage but the last, tighten the box to the nodes whose activated density exceeds this and spend the next stage's nodes inside it (negative: off)")
 @click.option("--tighten_margin", type=click.IntRange(min=0), required=False, default=1, help="nodes kept around the content box when tightening")
+@click.option("--report_ssim", type=click.BOOL, required=False, default=False, help="the periodic test also reports the held-out SSIM (test_ssim)")
 @click.option("--seed", type=click.INT, required=False, default=42, help="seed of torch's generators")
 # fmt: on
 # -------------------------------------------------------------------------------------
@@ -161,7 +162,7 @@ def main(**kwargs) -> None:
         global_batch=config["global_batch"], tv_density_weight=config["tv_density_weight"], tv_feature_weight=config["tv_feature_weight"],
         tv_epsilon=config["tv_epsilon"], distortion_weight=config["distortion_weight"], prune_threshold=config["prune_threshold"] if config["prune_threshold"] >= 0.0 else None,
         prune_dilate=config["prune_dilate"], tighten_threshold=config["tighten_threshold"] if config["tighten_threshold"] >= 0.0 else None,
-        tighten_margin=config["tighten_margin"],
+        tighten_margin=config["tighten_margin"], report_ssim=config["report_ssim"],
     )
 
 

@@ -47,6 +47,8 @@ from .composable import (  # noqa: F401  (the path at the granularity of the ref
 )
 from .mesh import Mesh, extract_mesh, write_ply  # noqa: F401
 from .ops import distortion_loss, render_geometry, total_variation  # noqa: F401
+from .metrics import ssim  # noqa: F401
+from .trainers import evaluate_sh_vox_grid_vol_mod_with_posed_images  # noqa: F401
 from .geometry import back_project_points, normal_map_image, write_point_cloud_ply  # noqa: F401
 from .pose_refinement import pose_error, refine_camera_pose  # noqa: F401
 from .pruning import PruneStats, node_max_weights, prune_voxel_grid  # noqa: F401

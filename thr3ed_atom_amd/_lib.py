@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "mesh_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "mesh_kernels.hip", "image_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -26,6 +26,9 @@ FLAG_AABB_SAMPLING = 4
 FLAG_OCCUPANCY_SKIP = 8
 FLAG_JITTER_KEYED = 16
 ERR_UNSUPPORTED = -3  # RF_ERR_UNSUPPORTED
+SSIM_PADDINGS = {"valid": 0, "same": 1}  # RF_SSIM_*
+SSIM_WINDOW = 11
+SSIM_TILE = (16, 32)  # map rows x columns per workgroup of rf_ssim_forward (image rows x columns of rf_ssim_backward)
 STEP_FORWARD = 1
 STEP_EMIT = 2
 STEP_BRICKS = 4
@@ -83,6 +86,9 @@ EXPORTED_SYMBOLS = [
     "rf_mesh_tiles",
     "rf_mesh_count",
     "rf_mesh_emit",
+    "rf_ssim_tiles",
+    "rf_ssim_forward",
+    "rf_ssim_backward",
 ]
 
 
@@ -226,6 +232,10 @@ class RFGeometryOut(C.Structure):
     _fields_ = [("normal_dev", C.c_void_p), ("quantile_depth_dev", C.c_void_p), ("acc_dev", C.c_void_p)]
 
 
+class RFImage(C.Structure):
+    _fields_ = [("data_dev", C.c_void_p), ("stride_h", C.c_int64), ("stride_w", C.c_int64), ("stride_c", C.c_int64)]
+
+
 TRAIN_STEP_EVENTS = 11
 def train_step_pairing():
     """(forward renders paired, emit launches paired): rf_train_step runs both renders of an iteration -- and both adjoints -- in ONE
@@ -240,7 +250,7 @@ TRAIN_STEP_EVENT_NAMES = ["select_rays_and_pixels", "render_forward[spec,save]",
 
 
 # order of rf_abi_struct_size(which)
-ABI_STRUCTS = [RFGrid, RFRayBatch, RFRenderOut, RFRenderGrads, RFBrickList, RFAdamState, RFCamera, RFRaySelection, RFPassScratch, RFTrainStep, RFGeometryOut]
+ABI_STRUCTS = [RFGrid, RFRayBatch, RFRenderOut, RFRenderGrads, RFBrickList, RFAdamState, RFCamera, RFRaySelection, RFPassScratch, RFTrainStep, RFGeometryOut, RFImage]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -337,9 +347,13 @@ def load() -> C.CDLL:
     lib.rf_mesh_tiles.argtypes = [C.POINTER(RFGrid), i32]
     lib.rf_mesh_count.argtypes = [C.POINTER(RFGrid), i32, f32, vp, vp]
     lib.rf_mesh_emit.argtypes = [C.POINTER(RFGrid), i32, f32, vp, i64, i64, vp, vp, vp, vp, vp, vp]
+    # image metrics (csrc/image_kernels.hip)
+    lib.rf_ssim_tiles.argtypes = [i32, i32, i32, i32]
+    lib.rf_ssim_forward.argtypes = [C.POINTER(RFImage), C.POINTER(RFImage), i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.rf_ssim_backward.argtypes = [C.POINTER(RFImage), C.POINTER(RFImage), i32, i32, i32, i32, vp, vp, C.POINTER(RFImage), vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
-            getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles") else C.c_int
+            getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int
     if lib.rf_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{LIB_PATH}: ABI version {lib.rf_abi_version()} != {ABI_VERSION} (stale build? run __graft_entry__.build())")
     lib.rf_abi_struct_size.argtypes = [C.c_int]

@@ -5246,6 +5246,7 @@ int rf_abi_struct_size(int which) {
     case 8: return (int)sizeof(RFPassScratch);
     case 9: return (int)sizeof(RFTrainStep);
     case 10: return (int)sizeof(RFGeometryOut);
+    case 11: return (int)sizeof(RFImage);
     default: return -1;
   }
 }

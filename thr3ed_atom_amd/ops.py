@@ -1725,3 +1725,94 @@ def adam_step_hip(param: Tensor, grad: Tensor, exp_avg: Tensor, exp_avg_sq: Tens
             param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), param.numel(), float(lr), float(beta1), float(beta2), float(eps), int(step), int(bool(zero_grad)), _stream(param.device)
         )
     _lib.check(rc, "rf_adam_step")
+
+
+# ---- image metrics (csrc/image_kernels.hip) ---------------------------------------------------------------------------------------
+def _image_struct(t: Tensor, name: str) -> "_lib.RFImage":
+    _require_hip(t, name)
+    if t.dim() != 3 or t.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 [H, W, C] tensor or view, got {t.dtype} {tuple(t.shape)}")
+    im = _lib.RFImage()
+    im.data_dev = t.data_ptr()
+    im.stride_h, im.stride_w, im.stride_c = (int(s) for s in t.stride())
+    return im
+
+
+def ssim_map_shape(height: int, width: int, padding: str) -> Tuple[int, int]:
+    """extent of the SSIM map of an H x W image: the image itself under "same", the windows inside it under "valid" """
+    if padding not in _lib.SSIM_PADDINGS:
+        raise ValueError(f'padding must be "valid" or "same", got {padding!r}')
+    if padding == "same":
+        return int(height), int(width)
+    if height < _lib.SSIM_WINDOW or width < _lib.SSIM_WINDOW:
+        raise ValueError(f'padding="valid" needs an image of at least {_lib.SSIM_WINDOW} x {_lib.SSIM_WINDOW} pixels, got {height} x {width}')
+    return int(height) - _lib.SSIM_WINDOW + 1, int(width) - _lib.SSIM_WINDOW + 1
+
+
+def ssim_forward_raw(image: Tensor, target: Tensor, padding: str = "valid", want_map: bool = False, want_derivatives: bool = False):
+    """Enqueue rf_ssim_forward (include/relu_field.h) on two float32 [H, W, C] tensors or views (any strides: nothing is copied).
+    Returns (mean, map, derivatives): the 0-d mean SSIM; the map as a [Hm, Wm, C] VIEW of planar storage, or None; the three
+    derivative maps rf_ssim_backward reads, [3, C, Hm, Wm], or None.  No autograd: metrics.ssim is the differentiable form."""
+    x, y = _image_struct(image, "image"), _image_struct(target, "target")
+    if tuple(image.shape) != tuple(target.shape):
+        raise ValueError(f"image {tuple(image.shape)} and target {tuple(target.shape)} must have the same shape")
+    H, W, Cn = (int(v) for v in image.shape)
+    if min(H, W, Cn) < 1:
+        raise ValueError(f"an image needs at least one pixel and one channel, got {tuple(image.shape)}")
+    hm, wm = ssim_map_shape(H, W, padding)
+    lib = _lib.load()
+    dev, code = image.device, _lib.SSIM_PADDINGS[padding]
+    tiles = int(lib.rf_ssim_tiles(H, W, Cn, code))
+    _lib.check(min(tiles, 0), "rf_ssim_tiles")
+    partials = torch.empty(tiles, dtype=torch.float32, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    planar = torch.empty((Cn, hm, wm), dtype=torch.float32, device=dev) if want_map else None
+    dmaps = torch.empty((3, Cn, hm, wm), dtype=torch.float32, device=dev) if want_derivatives else None
+    with _span("ssim_forward", dev):
+        rc = lib.rf_ssim_forward(C.byref(x), C.byref(y), H, W, Cn, code, _ptr(planar), _ptr(dmaps), _ptr(partials), _ptr(mean), _stream(dev))
+    _lib.check(rc, "rf_ssim_forward")
+    return mean, (None if planar is None else planar.permute(1, 2, 0)), dmaps
+
+
+def ssim_backward_raw(image: Tensor, target: Tensor, padding: str, derivatives: Tensor, grad_mean: Tensor, grad_image: Tensor) -> None:
+    """Enqueue rf_ssim_backward: ``grad_image`` (float32 [H, W, C], any strides) is OVERWRITTEN with grad_mean * d mean / d image from
+    the ``derivatives`` of the matching ssim_forward_raw call.  ``grad_mean`` is a one-element float32 device tensor the kernel reads."""
+    x, y, gx = _image_struct(image, "image"), _image_struct(target, "target"), _image_struct(grad_image, "grad_image")
+    H, W, Cn = (int(v) for v in image.shape)
+    hm, wm = ssim_map_shape(H, W, padding)
+    if tuple(target.shape) != (H, W, Cn) or tuple(grad_image.shape) != (H, W, Cn):
+        raise ValueError("image, target and grad_image must have the same shape")
+    if not (derivatives.is_cuda and derivatives.is_contiguous() and derivatives.dtype == torch.float32 and tuple(derivatives.shape) == (3, Cn, hm, wm)):
+        raise ValueError(f"derivatives must be the contiguous float32 [3, {Cn}, {hm}, {wm}] tensor of ssim_forward_raw")
+    _require_hip(grad_mean, "grad_mean")
+    if grad_mean.dtype != torch.float32 or grad_mean.numel() != 1:
+        raise ValueError("grad_mean must hold one float32")
+    dev = image.device
+    with _span("ssim_backward", dev):
+        rc = _lib.load().rf_ssim_backward(C.byref(x), C.byref(y), H, W, Cn, _lib.SSIM_PADDINGS[padding], _ptr(derivatives), _ptr(grad_mean), C.byref(gx),
+                                          _stream(dev))
+    _lib.check(rc, "rf_ssim_backward")
+
+
+class _SSIM(torch.autograd.Function):
+    """mean SSIM of (image, target), differentiable in ``image``.  The forward writes the three derivative maps only when ``image``
+    needs a gradient; the backward is one gather launch that reads the upstream scalar on the device."""
+
+    @staticmethod
+    def forward(ctx, image, target, padding, want_map):
+        needs = bool(ctx.needs_input_grad[0])
+        mean, smap, dmaps = ssim_forward_raw(image, target, padding, want_map, needs)
+        ctx.padding = padding
+        if needs:
+            ctx.save_for_backward(image, target, dmaps)
+        if smap is None:
+            return mean
+        ctx.mark_non_differentiable(smap)
+        return mean, smap
+
+    @staticmethod
+    def backward(ctx, g_mean, *_):
+        image, target, dmaps = ctx.saved_tensors
+        grad = torch.empty_like(image)  # (a dense view keeps its layout: a [C, H, W] leaf gets its gradient without a transpose)
+        ssim_backward_raw(image, target, ctx.padding, dmaps, g_mean.to(torch.float32).contiguous(), grad)
+        return grad, None, None, None

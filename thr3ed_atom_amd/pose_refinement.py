@@ -3,7 +3,7 @@
 The field is frozen: only the pose moves.  The pose is parametrised as a perturbation of an initial pose,
 R = so3_exp(omega) R0 and t = t0 + tau (camera.perturb_pose), and (omega, tau) are fitted with Adam on the reference's L1
 colour loss.  Every step goes cast_rays (HIP kernel, differentiable in R and t) -> render_rays (the fused HIP render,
-differentiable in the rays through rf_render_backward_rays) -> L1, so no grid gradient is ever computed.
+differentiable in the rays through rf_render_backward_rays) -> L1 (optionally mixed with D-SSIM), so no grid gradient is ever computed.
 """
 from typing import Any, Dict, List, Optional, Tuple
 
@@ -25,6 +25,7 @@ def refine_camera_pose(
     rays_per_iteration: Optional[int] = None,
     seed: int = 0,
     final_learning_rate_fraction: float = 0.01,
+    dssim_weight: float = 0.0,
     **render_kwargs,
 ) -> Tuple[CameraPose, List[Dict[str, Any]]]:
     """Fit the pose of ``image`` [H, W, 3] (values in [0, 1]) starting from ``initial_pose``.
@@ -32,7 +33,10 @@ def refine_camera_pose(
     The learning rate decays exponentially to ``final_learning_rate_fraction`` of ``learning_rate`` over the iterations (the L1
     loss's gradient does not shrink near the optimum, so a constant rate would leave the pose jittering at the step size).
     ``rays_per_iteration``: None renders every pixel per iteration; a number draws that many pixels per iteration, a keyed random
-    subset (seeded by ``seed`` and the iteration, reproducible).  ``render_kwargs`` override render-config fields for the renders
+    subset (seeded by ``seed`` and the iteration, reproducible).  ``dssim_weight`` = lambda in (0, 1]: the loss becomes
+    (1 - lambda) L1 + lambda (1 - SSIM) of the full frame, SSIM with the zero-padded "same" windows (the D-SSIM term of 3DGS, against
+    L1's flat basin; metrics.ssim); it needs the image, so it cannot be combined with ``rays_per_iteration`` below the frame.  0 is
+    the plain L1 path.  ``render_kwargs`` override render-config fields for the renders
     (the volumetric model's own configuration is used otherwise).  Returns the refined pose (float32 tensors on the model's device,
     t of shape [3, 1]) and the history: one dict per iteration with ``loss`` (of the pose before the step), ``rotation`` and
     ``translation`` (numpy, after the step)."""
@@ -41,6 +45,11 @@ def refine_camera_pose(
     target = torch.as_tensor(image).to(device, torch.float32).reshape(-1, 3)
     if target.shape[0] != int(H) * int(W):
         raise ValueError(f"image must be [{H}, {W}, 3], got {tuple(torch.as_tensor(image).shape)}")
+    dssim_weight = float(dssim_weight)
+    if not 0.0 <= dssim_weight <= 1.0:
+        raise ValueError(f"dssim_weight must lie in [0, 1], got {dssim_weight}")
+    if dssim_weight > 0.0 and rays_per_iteration is not None and int(rays_per_iteration) < target.shape[0]:
+        raise ValueError("dssim_weight > 0 needs the whole frame per iteration (SSIM is a function of the image): leave rays_per_iteration at None")
     pose0 = CameraPose(torch.as_tensor(initial_pose.rotation).to(device, torch.float32).reshape(3, 3),
                        torch.as_tensor(initial_pose.translation).to(device, torch.float32).reshape(3, 1))
     omega = torch.zeros(3, dtype=torch.float32, device=device, requires_grad=True)
@@ -65,6 +74,11 @@ def refine_camera_pose(
                 tgt = target[sel]
             out = vol_mod.render_rays(rays, **render_kwargs)
             loss = torch.nn.functional.l1_loss(out.colour, tgt)
+            if dssim_weight > 0.0:
+                from .metrics import ssim
+
+                frame = out.colour.reshape(int(H), int(W), 3)
+                loss = (1.0 - dssim_weight) * loss + dssim_weight * (1.0 - ssim(frame, tgt.reshape(int(H), int(W), 3), padding="same"))
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             optimizer.step()

@@ -1195,6 +1195,7 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     prune_dilate: int = 1,
     tighten_threshold: Optional[float] = None,
     tighten_margin: int = 1,
+    report_ssim: bool = False,
 ) -> VolumetricModel:
     """Same arguments (minus the feedback/visualisation ones) and same schedule as the reference's
     trainer.  Returns the trained model; ``history`` (if given) collects the logged scalars.
@@ -1216,7 +1217,9 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     activated density exceeds the threshold plus ``tighten_margin`` nodes, and the next stage's node budget
     prod(stage_sizes[stage]) is spent inside that box (resampling.tighten_voxel_grid: DVGO's rule); ``history`` gets a row with the
     old and new dims and boxes.  A field without such a node is up-scaled as usual.  Replicas of a process group hold identical
-    parameters, so every rank computes the same box: no communication."""
+    parameters, so every rank computes the same box: no communication.
+    ``report_ssim``: the periodic test also reports the mean SSIM of the held-out views (metrics.ssim, "valid" windows) as
+    ``test_ssim`` in its ``history`` row and in the log line; off, nothing new is computed, allocated or written."""
     grid = vol_mod.thre3d_repr
     assert isinstance(grid, VoxelGrid), f"cannot use a {type(grid)} with this TrainProcedure"
     assert vol_mod.render_procedure is render_sh_voxel_grid, "non SH-based VoxelGrids cannot be used with this TrainProcedure"
@@ -1290,11 +1293,18 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
             if it % lr_decay_steps_per_stage == 0:
                 scheduler.step()
             if test_dataset is not None and (global_step % test_freq == 0 or it == num_iterations_per_stage):
-                psnr = test_sh_vox_grid_vol_mod_with_posed_images(vol_mod, test_dataset)
-                if history is not None:
-                    history.append({"global_step": global_step, "test_psnr": psnr})
-                if is_main:
-                    log(f"TEST SET PSNR: {psnr:.3f}")
+                if report_ssim:
+                    scores = evaluate_sh_vox_grid_vol_mod_with_posed_images(vol_mod, test_dataset)
+                    if history is not None:
+                        history.append({"global_step": global_step, "test_psnr": scores["psnr"], "test_ssim": scores["ssim"]})
+                    if is_main:
+                        log(f"TEST SET PSNR: {scores['psnr']:.3f} SSIM: {scores['ssim']:.4f}")
+                else:
+                    psnr = test_sh_vox_grid_vol_mod_with_posed_images(vol_mod, test_dataset)
+                    if history is not None:
+                        history.append({"global_step": global_step, "test_psnr": psnr})
+                    if is_main:
+                        log(f"TEST SET PSNR: {psnr:.3f}")
                 last = time.perf_counter()
             if global_step % save_freq == 0 or it == 1 or it == num_iterations_per_stage:
                 save(f"model_stage_{stage}_iter_{global_step}.pth")
@@ -1367,3 +1377,30 @@ def test_sh_vox_grid_vol_mod_with_posed_images(
 
 
 test_sh_vox_grid_vol_mod_with_posed_images.__test__ = False  # not a pytest test
+
+
+def evaluate_sh_vox_grid_vol_mod_with_posed_images(
+    vol_mod: VolumetricModel, dataset: PosedImagesInMemory, parallel_rays_chunk_size: Optional[int] = 32768
+) -> dict:
+    """PSNR and SSIM over held-out images: ``{"psnr", "ssim", "per_image": [{"psnr", "ssim"}, ...]}``, the first two the means of the
+    per-image values.  The renders and the PSNR formula are those of test_sh_vox_grid_vol_mod_with_posed_images (``psnr`` is its
+    return value); SSIM is metrics.ssim with the "valid" windows of the NeRF literature, of the render [H, W, 3] against the
+    dataset's [3, H, W] image seen as [H, W, 3] -- no copy of either.  LPIPS needs network weights and stays out of scope."""
+    from .camera import CameraPose
+    from .metrics import ssim
+
+    cfg = vol_mod.render_config
+    per_image = []
+    with torch.no_grad():
+        for i in range(len(dataset)):
+            image, pose = dataset[i]
+            out = vol_mod.render(
+                CameraPose(pose[:, :3], pose[:, 3:]),
+                dataset.camera_intrinsics,
+                parallel_rays_chunk_size=parallel_rays_chunk_size,
+                optimized_sampling=False,
+                num_samples_per_ray=cfg.render_num_samples_per_ray,
+            )
+            target = image.permute(1, 2, 0)
+            per_image.append({"psnr": float(mse2psnr(mse_loss(out.colour, target))), "ssim": float(ssim(out.colour.to(torch.float32), target.to(torch.float32)))})
+    return {"psnr": float(np.mean([r["psnr"] for r in per_image])), "ssim": float(np.mean([r["ssim"] for r in per_image])), "per_image": per_image}
