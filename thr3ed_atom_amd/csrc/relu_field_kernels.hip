@@ -2805,7 +2805,9 @@ __host__ __device__ inline int gather_lds_words(int B, int C, int BX = 8) {
 // accumulator N[(c, x)][(y, z)] takes them: A = g_c(record) * wx(record, x), B = wy(record, y) * wz(record, z), four records per
 // v_mfma_f32_16x16x4_f32.  Wave w owns block w and ONE list of the records that touch it (1.56 blocks per record against 2.81 tiles;
 // every B column useful, where the tile form fed zeros to 12 of 16).  The blocks are added to channels 0..3 of the image after the
-// wide tiles: those channels are (sum of the full-width records) + (sum of the base-channel records).
+// wide tiles: those channels are (sum of the full-width records) + (sum of the base-channel records).  A base-channel record has
+// nothing to expand, so ONE thread does its whole record pass and a batch holds up to 256 of them (the workgroup's threads; what a
+// byte index allows): the average brick of the bench step sums its ~212 in one stage -> barrier -> lists + MFMAs -> barrier round.
 template <int K, bool ADAM, bool ONE_ROUND = false, bool SPLIT = false, int BX = 8, bool MIRROR = false>
 __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9 ? 2 : 4)) void brick_gather_kernel(GridArgs g, BrickArgs a, float* gdens, float* gfeat) {
   static_assert(BX == 8 || (BX == 4 && ONE_ROUND && !SPLIT), "4 x 8 x 8 bricks: 8-node y and z edges, one workgroup per brick");
@@ -2830,6 +2832,19 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
   __shared__ __attribute__((aligned(16))) int s_wstart[kMaxRangesKind], s_wcum[kMaxRangesKind + 8];  // ranges of the full-width lists: first record, running count
   __shared__ __attribute__((aligned(16))) int s_nstart[kMaxRangesKind], s_ncum[kMaxRangesKind + 8];  // ... of the base-channel lists of a mixed call
   __shared__ int s_part[4];
+  // SEP base-channel batches: up to TH records, one thread per record (a record has nothing to expand).  The block table holds the
+  // weight rows x 0..3, y 0..7, z 0..7 only, the record rows the four channel values, a mask is a byte and every wave has ONE list:
+  // all of it lives in the space of the full-width batch's buffers.  (Record rows 4 words apart: the 16 (record, channel) words an
+  // instruction reads collide in a bank only for records 16 apart, as with the padded rows.)
+  constexpr int GBN = SEP ? TH : GB;  // records per base-channel batch
+  constexpr int BROW = TH + 4;        // words of a block-table row
+  constexpr int NWB = TH / 64;        // mask words of a base-channel batch
+  float* btab = acc;                  // [4 + 8 + 8][BROW]
+  float* brows = acc + 20 * BROW;     // [TH][4]
+  unsigned char* bmask = reinterpret_cast<unsigned char*>(s_tmask);
+  unsigned char(*blist)[TH + 24] = reinterpret_cast<unsigned char(*)[TH + 24]>(&s_list[0][0]);  // [NWV]
+  static_assert(!SEP || (20 * BROW + 4 * TH <= GB * gather_record_words(C4) + GROW * kGatherWtab && TH <= kGatherBatch && NWV * (TH + 24) <= 4 * NWV * (GB + 24)),
+                "the base-channel batch of the separable form fits the full-width batch's buffers, its indices a byte");
   const int B = ONE_ROUND ? 8 : (1 << a.shift);  // (ONE_ROUND: 8^3 bricks only -- tile counts and image strides fold to constants)
   const int bshift = ONE_ROUND ? 3 : a.shift;
   const int SY = brick_row_stride(B, C), SX = brick_slab_stride(B, C);
@@ -2907,7 +2922,7 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
   f32x4 naccr = f32x4{0.f, 0.f, 0.f, 0.f};
 
   if (any) {
-    const int nba = (total + GB - 1) / GB, nbd = (total_d + GB - 1) / GB;
+    const int nba = (total + GB - 1) / GB, nbd = (total_d + GBN - 1) / GBN;
     uint32_t wprev = 0x00ffffffu;  // the lower nodes (c + 1, one byte per axis) this thread's record of the previous batch had; 0xff = none
     const int rec_id = tid & (GB - 1);  // this thread's record of every batch; the two threads of a record split its channels
     const int half = tid >= GB;
@@ -2916,10 +2931,8 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     // thread of the record), and its row of per-channel values.  A full-width record of an SH grid arrives COMPACT -- d density,
     // d raw r, g, b and the unit viewing direction -- and is expanded here, d raw[colour] * Y_k(v) in the operation order of the
     // reference's evaluate_spherical_harmonics, so that the expanded values never exist in HBM.
-    // (BLOCKS: a base-channel batch of the SEP form -- the mask holds the yz-blocks the record touches, bit 2 * (y >> 2) + (z >> 2))
-    auto stage = [&](auto expand_tag, auto blocks_tag, float4 q0, float4 q1, float4 q2, int nrec) {
+    auto stage = [&](auto expand_tag, float4 q0, float4 q1, float4 q2, int nrec) {
       constexpr bool EXPAND = decltype(expand_tag)::value;
-      constexpr bool BLOCKS = decltype(blocks_tag)::value;
       constexpr int RW = gather_record_words(EXPAND ? C4 : 4);
       if (half == 0) {
         uint32_t tm = 0, wnow = 0x00ffffffu;
@@ -2941,7 +2954,7 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
           for (int ax = 0; ax < 3; ++ax) {
             const float fl = floorf(idx[ax]);
             const int c = (int)fl - org[ax];  // lower node of the cell relative to the brick: -1 .. B - 1
-            const int sh = (BLOCKS && ax > 0) || ax == 2 ? 2 : 1;
+            const int sh = ax == 2 ? 2 : 1;
             uint32_t bits = 0;
             if (c >= 0) {
               wcol[(ax * 8 + c) * GROW] = (fl + 1.0f) - idx[ax];  // same arithmetic as locate()
@@ -2954,17 +2967,13 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
             pb[ax] = bits;
             wnow |= (uint32_t)(c + 1) << (8 * ax);
           }
-          if constexpr (BLOCKS) {
-            if (pb[0]) tm = ((pb[1] & 1u) ? pb[2] : 0u) | ((pb[1] & 2u) ? pb[2] << 2 : 0u);
-          } else {
-            uint32_t yz = 0;
+          uint32_t yz = 0;
 #pragma unroll
-            for (int py = 0; py < 4; ++py)
-              if ((pb[1] >> py) & 1u) yz |= pb[2] << (py * npz);
+          for (int py = 0; py < 4; ++py)
+            if ((pb[1] >> py) & 1u) yz |= pb[2] << (py * npz);
 #pragma unroll
-            for (int px = 0; px < 4; ++px)
-              if ((pb[0] >> px) & 1u) tm |= yz << (px * npy * npz);
-          }
+          for (int px = 0; px < 4; ++px)
+            if ((pb[0] >> px) & 1u) tm |= yz << (px * npy * npz);
         }
         wprev = wnow;
         s_tmask[rec_id] = tm;
@@ -2991,6 +3000,48 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
       } else {
         if (half == 0) *reinterpret_cast<float4*>(row) = q1;
       }
+    };
+    // -- SEP: the record pass of a base-channel batch.  Thread tid does all of record tid: its column of the block table (entries of
+    // the previous base-channel batch un-written first), the set of yz-blocks it touches (bit 2 * (y >> 2) + (z >> 2)), its four
+    // channel values.
+    auto stage_blocks = [&](float4 q0, float4 q1, int nrec) {
+      uint32_t tm = 0, wnow = 0x00ffffffu;
+      float* wcol = btab + tid;
+      constexpr int first_row[3] = {0, 4, 12}, nodes[3] = {4, 8, 8};
+#pragma unroll
+      for (int ax = 0; ax < 3; ++ax) {
+        const int c1 = (int)((wprev >> (8 * ax)) & 0xffu);  // c + 1
+        if (c1 != 0xff) {
+          if (c1 >= 1) wcol[(first_row[ax] + c1 - 1) * BROW] = 0.0f;
+          if (c1 < nodes[ax]) wcol[(first_row[ax] + c1) * BROW] = 0.0f;
+        }
+      }
+      if (tid < nrec) {
+        const float idx[3] = {q0.x, q0.y, q0.z};
+        const int org[3] = {X0, Y0, Z0};
+        uint32_t pb[3];
+        wnow = 0;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+          const float fl = floorf(idx[ax]);
+          const int c = (int)fl - org[ax];  // lower node of the cell relative to the brick: -1 .. nodes - 1
+          uint32_t bits = 0;
+          if (c >= 0) {
+            wcol[(first_row[ax] + c) * BROW] = (fl + 1.0f) - idx[ax];  // same arithmetic as locate()
+            bits |= 1u << (c >> 2);
+          }
+          if (c + 1 < nodes[ax]) {
+            wcol[(first_row[ax] + c + 1) * BROW] = idx[ax] - fl;
+            bits |= 1u << ((c + 1) >> 2);
+          }
+          pb[ax] = bits;
+          wnow |= (uint32_t)(c + 1) << (8 * ax);
+        }
+        if (pb[0]) tm = ((pb[1] & 1u) ? pb[2] : 0u) | ((pb[1] & 2u) ? pb[2] << 2 : 0u);
+      }
+      wprev = wnow;
+      bmask[tid] = (unsigned char)tm;
+      *reinterpret_cast<float4*>(brows + 4 * tid) = q1;
     };
     // -- bin the batch to the tiles it touches and multiply it into the tiles' accumulators (WIDE: rows of C4 channels, else 4)
     auto process = [&](auto wide_tag, int nrec) {
@@ -3103,7 +3154,6 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     // record order), then the same two-deep pipeline of LDS requests as the tile loop: four reads per lane and instruction (g, wx,
     // wy, wz), the products formed in registers
     auto process_blocks = [&](int nrec) {
-      constexpr int RW = gather_record_words(4);
       RF_PROF_MARK(7);
       __syncthreads();
       RF_PROF_MARK(2);
@@ -3112,13 +3162,13 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
 #else
       constexpr bool no_lists = false, no_tiles = false;
 #endif
-      unsigned char* list = s_list[wave];
+      unsigned char* list = blist[wave];
       int n = 0;
       if (!no_lists)
 #pragma unroll
-        for (int wd = 0; wd < NW; ++wd) {
+        for (int wd = 0; wd < NWB; ++wd) {
           if (wd * 64 >= nrec) break;
-          const bool hit = (s_tmask[wd * 64 + lane] >> wave) & 1u;
+          const bool hit = (bmask[wd * 64 + lane] >> wave) & 1u;
           const unsigned long long m = __ballot(hit);
           const int pos = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
           if (hit) list[pos] = (unsigned char)(wd * 64 + lane);
@@ -3128,10 +3178,10 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
       if (n > 0 && !no_tiles) {
         // A row (c, x) = (mi >> 2, mi & 3); B column (y, z) = (4 (wave >> 1) + (jj >> 2), 4 (wave & 1) + (jj & 3))
         const uint32_t a_list = lds_offset(list) + kk;
-        const uint32_t a_x = lds_offset(wtab + (mi & 3) * GROW);
-        const uint32_t a_y = lds_offset(wtab + (8 + 4 * (wave >> 1) + (jj >> 2)) * GROW);
-        const uint32_t a_z = lds_offset(wtab + (16 + 4 * (wave & 1) + (jj & 3)) * GROW);
-        const uint32_t a_g = lds_offset(rows + (mi >> 2));
+        const uint32_t a_x = lds_offset(btab + (mi & 3) * BROW);
+        const uint32_t a_y = lds_offset(btab + (4 + 4 * (wave >> 1) + (jj >> 2)) * BROW);
+        const uint32_t a_z = lds_offset(btab + (12 + 4 * (wave & 1) + (jj & 3)) * BROW);
+        const uint32_t a_g = lds_offset(brows + (mi >> 2));
         const int nq = (n + 3) >> 2;
         uint32_t ra = 0, rb = 0;
         float xa = 0.f, ya = 0.f, za = 0.f, ga = 0.f, xb = 0.f, yb = 0.f, zb = 0.f, gb = 0.f;  // (sets A, B)
@@ -3139,7 +3189,7 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
           lds_request_f32<0>(wx, a_x + 4 * r);
           lds_request_f32<0>(wy, a_y + 4 * r);
           lds_request_f32<0>(wz, a_z + 4 * r);
-          lds_request_f32<0>(g, a_g + (uint32_t)__umul24(r, RW * 4));
+          lds_request_f32<0>(g, a_g + 16 * r);
         };
         auto multiply = [&](float wx, float wy, float wz, float g, int q) {
           const float av = g * wx;
@@ -3172,9 +3222,10 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     using Yes = std::integral_constant<bool, true>;
     using No = std::integral_constant<bool, false>;
 
-    // global loads of a batch straight into registers -- every thread the quads of ITS record (the two threads of a record
-    // both: the second copy is an L1 hit) --, issued one batch ahead of their use; always unconditional and clamped, with their
-    // own registers per list kind (a conditionally assigned register is merged with a copy, and the copy waits for the load)
+    // global loads of a batch straight into registers -- every thread the quads of ITS record (the two threads of a full-width record
+    // both: the second copy is an L1 hit; of a base-channel record of the SEP form its one thread alone) --, issued one batch ahead of
+    // their use; always unconditional and clamped, with their own registers per list kind (a conditionally assigned register is merged
+    // with a copy, and the copy waits for the load)
     int sri = 0, dri = 0;  // running range index of this thread (its records only move forward), the range's bounds cached
     int rlo = 0, rhi = 0, dlo = 0, dhi = 0;
     const float4* rptr = a.wide[SPLIT ? min(part, kMaxListsPerKind - 1) : 0].rec;    // list base + (start of the range - its position in the concatenation)
@@ -3209,8 +3260,8 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
       if constexpr (QW > 2) w2 = load_f4<RF_NT_RECORD_LOAD>(p + 2);
     };
     auto fetch_narrow = [&](int sd) {
-      const int nrec = min(GB, total_d - sd * GB);
-      const int v = sd * GB + min(rec_id, nrec - 1);
+      const int nrec = min(GBN, total_d - sd * GBN);
+      const int v = sd * GBN + min(SEP ? tid : rec_id, nrec - 1);  // (SEP: one thread per record, and nobody else loads it)
       if (v < dlo || v >= dhi) {
         dri = range_of(s_ncum, v, nnarrow_p, dri);
         dlo = s_ncum[dri];
@@ -3225,22 +3276,36 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
     if (nba > 0) fetch_wide(0);
     // (behind the first batches' loads:) the weight table starts zero-filled; a record's thread clears the entries of the previous
     // batch before it writes new ones
-    for (int i = tid; i < GROW * kGatherWtab / 4; i += TH) reinterpret_cast<float4*>(wtab)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    __syncthreads();
+    if (!SEP || nba > 0) {  // (uniform)
+      for (int i = tid; i < GROW * kGatherWtab / 4; i += TH) reinterpret_cast<float4*>(wtab)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      __syncthreads();
+    }
     for (int s = 0; s < nba; ++s) {
       const int nrec = min(GB, total - s * GB);
       if constexpr (K > 1)
-        stage(Yes{}, No{}, w0, w1, w2, nrec);
+        stage(Yes{}, w0, w1, w2, nrec);
       else
-        stage(No{}, No{}, w0, w1, w2, nrec);
+        stage(No{}, w0, w1, w2, nrec);
       RF_PROF_MARK(1);  // waiting for the batch's loads, record pass
       fetch_wide(min(s + 1, nba - 1));  // (the last batch again at the end: cheaper than a conditional)
       RF_PROF_MARK(6);  // issuing the next batch's loads
       process(Yes{}, nrec);
     }
+    if constexpr (SEP) {
+      // the block table has another shape than the weight table and lies over the full-width rows: every thread clears its own column
+      // (no barrier: nobody else writes it), behind the loads of the first base-channel batch, which have been in flight since the top
+      if (nbd > 0) {
+#pragma unroll
+        for (int r = 0; r < 20; ++r) btab[r * BROW + tid] = 0.0f;
+        wprev = 0x00ffffffu;
+      }
+    }
     for (int sd = 0; sd < nbd; ++sd) {
-      const int nrec = min(GB, total_d - sd * GB);
-      stage(No{}, std::integral_constant<bool, SEP>{}, d0, d1, d1, nrec);
+      const int nrec = min(GBN, total_d - sd * GBN);
+      if constexpr (SEP)
+        stage_blocks(d0, d1, nrec);
+      else
+        stage(No{}, d0, d1, d1, nrec);
       RF_PROF_MARK(1);
       fetch_narrow(min(sd + 1, nbd - 1));
       RF_PROF_MARK(6);
