@@ -16,7 +16,7 @@
  *    never allocates, frees or retains them.  All tensors are contiguous float32 unless a stride is given.
  *  - Every call only ENQUEUES work on `stream` (a hipStream_t passed as void*); no implicit synchronisation.
  *  - Re-entrant: no mutable state is shared between calls.  What the library keeps per process is read-only after its first
- *    use: tuning knobs read from the environment ($RF_FRAME_TILES, $RF_FWD_PAIR, $RF_EMIT_PAIR, $RF_BRICK_STAGGER, $RF_FAR_ADDRESSING -- A/B switches,
+ *    use: tuning knobs read from the environment ($RF_FRAME_TILES, $RF_FWD_PAIR, $RF_EMIT_PAIR, $RF_BRICK_STAGGER, $RF_FAR_ADDRESSING, $RF_STEP_SPECIALISED -- A/B switches,
  *    unset in production) and the cached result of one-time hipFuncSetAttribute calls (dynamic LDS size of the brick kernels).
  *    Return value: RF_OK (0) or a negative RF_ERR_* code; nothing is thrown across the ABI.  rf_error_string() maps a code to text.
  *  - Gradient buffers are ACCUMULATED into (+=) with float32 hardware atomics; the caller zero-fills them
@@ -710,6 +710,18 @@ int rf_bin_offsets_pair(const int32_t* const* hist_dev, int32_t num_keys, int64_
                         void* stream);
 int rf_render_backward_emit_direct_pair(const RFGrid* grid, const RFRayBatch* rays, const uint32_t* flags,
                                         const RFPassScratch* passes, void* stream);
+
+/* Which instantiation of the two pair kernels (rf_render_forward_pair, rf_render_backward_emit_direct_pair, and the same launches
+ * inside rf_train_step) serves this grid, these two ray batches and these two flag words: 1 = the TRAINER-SHAPED one, 0 = the
+ * generic one; negative = error code (RF_ERR_UNSUPPORTED when the two renders do not pair up).  Trainer-shaped means, all of:
+ * layout RF_LAYOUT_SPLIT (not bricked), a grid small enough for 32-bit corner offsets (<= 2^24 nodes, both tensors inside one 4 GB
+ * window; $RF_FAR_ADDRESSING = 1 switches that off), density_mode RF_DENSITY_RELU, both batches ray lists (camera == NULL) with
+ * t_rand_dev == NULL and RF_FLAG_JITTER_KEYED, neither RF_FLAG_OCCUPANCY_SKIP nor RF_FLAG_AABB_SAMPLING.  RF_FLAG_WHITE_BKGD may
+ * be either.  The trainer-shaped kernels run the same per-sample code with those switches compiled in instead of read from
+ * their arguments: every output is bit for bit the generic kernels'.  $RF_STEP_SPECIALISED = 0 in the environment (read at every
+ * call) sends everything to the generic kernels.  Host-side only: no device access.  (Added to ABI version 4 compatibly: no
+ * existing struct or signature changed.) */
+int rf_step_kernel_specialised(const RFGrid* grid, const RFRayBatch* rays, const uint32_t* flags);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,7 @@ EXPORTED_SYMBOLS = [
     "rf_l1_loss_grad_pair",
     "rf_bin_offsets_pair",
     "rf_render_backward_emit_direct_pair",
+    "rf_step_kernel_specialised",
     "rf_mesh_tiles",
     "rf_mesh_count",
     "rf_mesh_emit",
@@ -343,6 +344,7 @@ def load() -> C.CDLL:
     lib.rf_l1_loss_grad_pair.argtypes = [C.POINTER(vp), vp, i64, f32, C.POINTER(vp), vp, vp, vp]
     lib.rf_bin_offsets_pair.argtypes = [C.POINTER(vp), i32, C.POINTER(vp), C.POINTER(vp), vp]
     lib.rf_render_backward_emit_direct_pair.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), C.POINTER(u32), C.POINTER(RFPassScratch), vp]
+    lib.rf_step_kernel_specialised.argtypes = [C.POINTER(RFGrid), C.POINTER(RFRayBatch), C.POINTER(u32)]
     # iso-surface extraction (csrc/mesh_kernels.hip)
     lib.rf_mesh_tiles.argtypes = [C.POINTER(RFGrid), i32]
     lib.rf_mesh_count.argtypes = [C.POINTER(RFGrid), i32, f32, vp, vp]

@@ -1203,7 +1203,49 @@ struct ForwardPair {
   OutArgs out[2];
   uint32_t flags[2];
 };
-template <int K>
+// The pair kernels of a TRAINER-SHAPED iteration (STEP = true; the host's rule: step_pair_specialised).  The per-ray bodies keep every
+// wave-uniform run-time switch of the ABI alive across their chunk loops -- storage layout, node order, near / far addressing, density
+// mode, occupancy mask, jitter table / keyed jitter, ray list / camera with its pose -- and with ~158 dwords of kernel arguments the
+// register allocator parks whole 16-register tuples of them in vector lanes (K = 9 forward pair: 154 v_writelane_b32 / 399
+// v_readlane_b32, 221 of the reloads inside the specular chunk loop -- vector-ALU issue slots of a kernel that is bound by them).
+// None of these switches ever changes in training: split storage in linear node order, near addressing, ReLU, ray lists, keyed
+// jitter without a table, no occupancy skip, no per-ray AABB bounds.  The specialised instantiation overwrites those fields of its
+// LOCAL argument copies with the rule's constants and calls the same per-ray body: constant propagation drops the branches not taken
+// and the registers that fed them.  No arithmetic changes -- both instantiations compute every value with the same operations.
+__device__ __forceinline__ void fold_step_switches(GridArgs& g, RayArgs& r, uint32_t& flags) {
+  g.layout = RF_LAYOUT_SPLIT;
+  g.bricked = 0;
+  g.near32 = 1;
+  g.mode = RF_DENSITY_RELU;
+  g.occ = nullptr;
+  g.step[2] = 1u;  // (linear node order: z fastest, and a brick edge is no jump)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) g.jump[a] = g.step[a];
+  r.trand = nullptr;
+  r.jitter = 1;
+  r.cam = 0;
+  r.H = r.W = 1;
+  r.focal = 1.0f;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) r.pose[i] = 0.0f;
+  flags &= ~(uint32_t)(RF_FLAG_OCCUPANCY_SKIP | RF_FLAG_AABB_SAMPLING);
+}
+
+// one ray of a pair launch: the per-ray body on the kernel's arguments as they are, or (STEP) on local copies with the switches folded
+template <int K, bool DIFFUSE, bool STEP>
+__device__ __forceinline__ void forward_pair_ray(const GridArgs& g, const RayArgs& r, const OutArgs& out, uint32_t flags, long long ray, int lane,
+                                                 uint32_t* my_entry, float* my_rgb) {
+  if constexpr (STEP) {
+    GridArgs gl = g;
+    RayArgs rl = r;
+    fold_step_switches(gl, rl, flags);
+    render_forward_ray<K, DIFFUSE, true>(gl, rl, out, flags, ray, lane, my_entry, my_rgb);
+  } else {
+    render_forward_ray<K, DIFFUSE, true>(g, r, out, flags, ray, lane, my_entry, my_rgb);
+  }
+}
+
+template <int K, bool STEP>
 __global__ __launch_bounds__(kBlock, RF_FWD_WAVES) void render_forward_pair_kernel(GridArgs g, ForwardPair p) {
   __shared__ __attribute__((aligned(16))) uint32_t s_entry[kWavesPerBlock][kWave * kEntryFwd];
   __shared__ __attribute__((aligned(16))) float s_rgb[kWavesPerBlock][kWave * 4];
@@ -1212,11 +1254,11 @@ __global__ __launch_bounds__(kBlock, RF_FWD_WAVES) void render_forward_pair_kern
   const long long ray = (long long)blockIdx.x * (kWavesPerBlock / 2) + (wave & 1);
   if (wave < 2) {
     if constexpr (K == 1)
-      render_forward_ray<1, true, true>(g, p.r[0], p.out[0], p.flags[0], ray, lane, s_entry[wave], s_rgb[wave]);
+      forward_pair_ray<1, true, STEP>(g, p.r[0], p.out[0], p.flags[0], ray, lane, s_entry[wave], s_rgb[wave]);
     else
-      render_forward_ray<K, false, true>(g, p.r[0], p.out[0], p.flags[0], ray, lane, s_entry[wave], s_rgb[wave]);
+      forward_pair_ray<K, false, STEP>(g, p.r[0], p.out[0], p.flags[0], ray, lane, s_entry[wave], s_rgb[wave]);
   } else {
-    render_forward_ray<1, true, true>(g, p.r[1], p.out[1], p.flags[1], ray, lane, s_entry[wave], s_rgb[wave]);
+    forward_pair_ray<1, true, STEP>(g, p.r[1], p.out[1], p.flags[1], ray, lane, s_entry[wave], s_rgb[wave]);
   }
 }
 
@@ -2142,7 +2184,19 @@ struct EmitPair {
   GradArgs gr[2];
   uint32_t flags[2];
 };
-template <int K>
+template <int K, bool DIFFUSE, bool STEP>
+__device__ __forceinline__ void emit_pair_ray(const GridArgs& g, const RayArgs& r, const OutArgs& fwd, const GradArgs& gr, uint32_t flags, long long ray, int lane) {
+  if constexpr (STEP) {  // (the trainer-shaped iteration: fold_step_switches)
+    GridArgs gl = g;
+    RayArgs rl = r;
+    fold_step_switches(gl, rl, flags);
+    render_emit_direct_ray<K, DIFFUSE>(gl, rl, fwd, gr, flags, ray, lane);
+  } else {
+    render_emit_direct_ray<K, DIFFUSE>(g, r, fwd, gr, flags, ray, lane);
+  }
+}
+
+template <int K, bool STEP>
 __global__ __launch_bounds__(kBlock, RF_EMIT_WAVES) void render_emit_direct_pair_kernel(GridArgs g, EmitPair p) {
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2155,11 +2209,11 @@ __global__ __launch_bounds__(kBlock, RF_EMIT_WAVES) void render_emit_direct_pair
   gr.hist_clear = nullptr;
   if (wave < 2) {
     if constexpr (K == 1)
-      render_emit_direct_ray<1, true>(g, p.r[0], p.fwd[0], gr, p.flags[0], ray, lane);
+      emit_pair_ray<1, true, STEP>(g, p.r[0], p.fwd[0], gr, p.flags[0], ray, lane);
     else
-      render_emit_direct_ray<K, false>(g, p.r[0], p.fwd[0], gr, p.flags[0], ray, lane);
+      emit_pair_ray<K, false, STEP>(g, p.r[0], p.fwd[0], gr, p.flags[0], ray, lane);
   } else {
-    render_emit_direct_ray<1, true>(g, p.r[1], p.fwd[1], gr, p.flags[1], ray, lane);
+    emit_pair_ray<1, true, STEP>(g, p.r[1], p.fwd[1], gr, p.flags[1], ray, lane);
   }
 }
 
@@ -5556,6 +5610,33 @@ int rf_render_forward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags
   });
 }
 
+// Which instantiation a pair launch gets: the one with the run-time switches folded (fold_step_switches) for the TRAINER-SHAPED
+// iteration -- split storage in linear node order, near addressing, ReLU density, both batches ray lists with keyed jitter and no
+// jitter table, neither occupancy skip nor per-ray AABB bounds: what TrainStepper's defaults (and the strict drop-in's split shadow)
+// always ask for -- and the generic one for everything else.  RF_FLAG_WHITE_BKGD stays a run-time flag.  $RF_STEP_SPECIALISED = 0
+// sends every pair launch to the generic instantiation (read per call: A/B runs and tests take both paths in one process).
+static bool step_pair_specialised(const RFGrid* grid, const GridArgs& g, const RFRayBatch* const rays[2], const uint32_t flags[2]) {
+  if (!(grid->layout == RF_LAYOUT_SPLIT && g.layout == RF_LAYOUT_SPLIT && !g.bricked && g.near32 && grid->density_mode == RF_DENSITY_RELU)) return false;
+  for (int i = 0; i < 2; ++i) {
+    if (rays[i]->camera || rays[i]->t_rand_dev || !(flags[i] & RF_FLAG_JITTER_KEYED)) return false;
+    if (flags[i] & (RF_FLAG_OCCUPANCY_SKIP | RF_FLAG_AABB_SAMPLING)) return false;
+  }
+  return env_flag("RF_STEP_SPECIALISED", true);
+}
+
+int rf_step_kernel_specialised(const RFGrid* grid, const RFRayBatch* rays, const uint32_t* flags) {
+  int rc = check_grid(grid);
+  if (rc != RF_OK) return rc;
+  if (!rays || !flags) return RF_ERR_NULL_POINTER;
+  const RFRayBatch* const rr[2] = {&rays[0], &rays[1]};
+  for (int i = 0; i < 2; ++i) {
+    rc = check_rays(rr[i]);
+    if (rc != RF_OK) return rc;
+  }
+  if (!renders_pair_up(rr, flags)) return RF_ERR_UNSUPPORTED;
+  return step_pair_specialised(grid, to_args(grid), rr, flags) ? 1 : 0;
+}
+
 // both saving forward renders of a training iteration (0 = specular, 1 = render_diffuse) over the same rays in ONE launch
 // (render_forward_pair_kernel); RF_ERR_UNSUPPORTED when the two calls do not pair up -- the caller then launches them one by one
 static int forward_pair_impl(const RFGrid* grid, const RFRayBatch* const rays[2], const uint32_t flags[2], const RFRenderOut* const outs[2], void* stream) {
@@ -5581,8 +5662,12 @@ static int forward_pair_impl(const RFGrid* grid, const RFRayBatch* const rays[2]
   if (rays[0]->num_rays == 0) return RF_OK;
   const GridArgs g = to_args(grid);
   const unsigned blocks = (unsigned)((rays[0]->num_rays + 1) / 2);
+  const bool specialised = step_pair_specialised(grid, g, rays, flags);
   return dispatch_sh(grid->num_features / 3, ShAll{}, [&](auto k) {
-    hipLaunchKernelGGL((render_forward_pair_kernel<decltype(k)::value>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
+    if (specialised)
+      hipLaunchKernelGGL((render_forward_pair_kernel<decltype(k)::value, true>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
+    else
+      hipLaunchKernelGGL((render_forward_pair_kernel<decltype(k)::value, false>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
     return launch_status();
   });
 }
@@ -5667,8 +5752,12 @@ static int emit_pair_impl(const RFGrid* grid, const RFRayBatch* const rays[2], c
   if (rays[0]->num_rays == 0) return RF_OK;
   const GridArgs g = to_args(grid);
   const unsigned blocks = (unsigned)((rays[0]->num_rays + 1) / 2);
+  const bool specialised = step_pair_specialised(grid, g, rays, flags);
   return dispatch_sh(grid->num_features / 3, ShAll{}, [&](auto k) {
-    hipLaunchKernelGGL((render_emit_direct_pair_kernel<decltype(k)::value>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
+    if (specialised)
+      hipLaunchKernelGGL((render_emit_direct_pair_kernel<decltype(k)::value, true>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
+    else
+      hipLaunchKernelGGL((render_emit_direct_pair_kernel<decltype(k)::value, false>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, p);
     return launch_status();
   });
 }

@@ -28,6 +28,10 @@ BENCH_NAMES = {
     "render_forward_kernel<9, false, true>": "render_forward[spec,save]",
     "render_forward_kernel<1, true, true>": "render_forward[diffuse,save]",
     "render_forward_pair_kernel<9>": "render_forward[spec+diffuse,save]",
+    "render_forward_pair_kernel<9, true>": "render_forward[spec+diffuse,save]",
+    "render_forward_pair_kernel<9, false>": "render_forward[spec+diffuse,save]",
+    "render_emit_direct_pair_kernel<9, true>": "render_backward_emit_direct[spec+diffuse]",
+    "render_emit_direct_pair_kernel<9, false>": "render_backward_emit_direct[spec+diffuse]",
     "render_forward_pair_kernel": "render_forward[spec+diffuse,save]",
     "render_emit_direct_pair_kernel": "render_backward_emit_direct[spec+diffuse]",
     "render_emit_direct_pair_kernel<9>": "render_backward_emit_direct[spec+diffuse]",
