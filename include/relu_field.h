@@ -363,6 +363,12 @@ int rf_brick_accumulate_adam_split(const RFGrid* grid, int32_t brick_size, const
                                    const RFAdamState* adam, int32_t first_brick, int32_t num_bricks, int32_t parts, void* scratch_dev,
                                    int64_t scratch_bytes, void* stream);
 
+/* ---- beside the render path and the training step (those, i.e. whatever no unit is named for: csrc/relu_field_kernels.hip) ----
+ * csrc/grid_kernels.hip      rf_grid_query, rf_grid_query_backward, rf_build_occupancy, rf_upsample_grid, rf_convert_grid,
+ *                            rf_tv_grad, rf_prune_grid, rf_node_bounds, rf_resample_grid
+ * csrc/ray_grad_kernels.hip  rf_grid_query_backward_points, rf_render_backward_rays
+ * csrc/ray_walk_kernels.hip  rf_node_max_weight, rf_distortion, rf_render_geometry */
+
 /* VoxelGrid.forward (thre3d_reprs/voxels.py:276-331) as a standalone point query: points_dev [M,3] (any
  * points: zeros padding outside the grid, no AABB mask) -> out_dev [M, F+1] = (F interpolated features in the
  * reference order colour*K + k, activated density).  Bit-for-bit the ATen grid_sample recipe. */

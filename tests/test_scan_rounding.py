@@ -1,4 +1,4 @@
-"""Why the forward kernels scan a chunk's transmittance in two forms (relu_field_kernels.hip: wave_incl_scan_trans): a float32 numpy
+"""Why the forward kernels scan a chunk's transmittance in two forms (csrc/rf_device.h: wave_incl_scan_trans): a float32 numpy
 re-enactment of the three scan orders on the ray that showed the problem in the randomised sweep -- 1000 samples of a slowly varying
 low density (alpha ~ 1.25e-4) and a last sample that takes what is left (alpha = 1: the reference's 1e10-long last interval inside
 the volume), so that the accumulated weight is exactly 1 in exact arithmetic.

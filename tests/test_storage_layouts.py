@@ -1,5 +1,5 @@
 """Host-side storage conversions (no GPU): reference <-> split <-> bricked are exact inverses and the brick-major node
-order matches the kernels' node_lin() formula (thr3ed_atom_amd/csrc/relu_field_kernels.hip)."""
+order matches the kernels' node_lin() formula (thr3ed_atom_amd/csrc/rf_device.h)."""
 import pytest
 import torch
 

@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "mesh_kernels.hip", "image_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -254,12 +254,17 @@ TRAIN_STEP_EVENT_NAMES = ["select_rays_and_pixels", "render_forward[spec,save]",
 ABI_STRUCTS = [RFGrid, RFRayBatch, RFRenderOut, RFRenderGrads, RFBrickList, RFAdamState, RFCamera, RFRaySelection, RFPassScratch, RFTrainStep, RFGeometryOut, RFImage]
 
 
+def build_inputs():
+    """Every file whose modification makes the library stale: the units of SOURCES, every private header of csrc/, the public header."""
+    headers = sorted(f for f in os.listdir(CSRC_DIR) if f.endswith(".h"))
+    return [os.path.join(CSRC_DIR, f) for f in SOURCES + headers] + [os.path.join(INCLUDE_DIR, "relu_field.h")]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Cross-compile the HIP sources for gfx950 into csrc/librelu_field_hip.so (hipcc needs no GPU)."""
     srcs = [os.path.join(CSRC_DIR, s) for s in SOURCES]
-    deps = srcs + [os.path.join(INCLUDE_DIR, "relu_field.h")]
     if not force and os.path.exists(LIB_PATH):
-        if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
+        if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in build_inputs()):
             return LIB_PATH
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc] + HIPCC_FLAGS + ["-I", INCLUDE_DIR] + srcs + ["-o", LIB_PATH]

@@ -22,12 +22,7 @@
 // d_sxx = dS / d s_xx, d_sxy = dS / d s_xy) and gathers, per image pixel p,
 //   dL/dx_p = (g / N) * [ (G*d_mu)_p + 2 x_p (G*d_sxx)_p + y_p (G*d_sxy)_p ]      (derivative maps are 0 outside the map's extent)
 // with the same staging / row pass / column pass.  g is read from device memory by the kernel.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include <cmath>
-
-#include "relu_field.h"
+#include "rf_device.h"
 
 namespace {
 
@@ -36,7 +31,7 @@ constexpr int kTileH = 16, kTileW = 32;     // map pixels per workgroup (rf_ssim
 constexpr int kInH = kTileH + kWin - 1;     // staged rows: 26
 constexpr int kInW = kTileW + kWin - 1;     // staged columns: 42
 constexpr int kImgBlock = 256;
-constexpr float kC1 = 1e-4f, kC2 = 9e-4f;   // 0.01^2, 0.03^2
+constexpr float kSsimC1 = 1e-4f, kSsimC2 = 9e-4f;  // 0.01^2, 0.03^2
 
 struct ImgView {
   float* p;
@@ -127,8 +122,8 @@ __global__ __launch_bounds__(kImgBlock) void ssim_forward_kernel(const SsimArgs 
     }
     const float mxmy = mx * my, mx2 = mx * mx, my2 = my * my;
     const float sxx = xx - mx2, syy = yy - my2, sxy = xy - mxmy;
-    const float A1 = 2.0f * mxmy + kC1, A2 = 2.0f * sxy + kC2;
-    const float B1 = mx2 + my2 + kC1, B2 = sxx + syy + kC2;
+    const float A1 = 2.0f * mxmy + kSsimC1, A2 = 2.0f * sxy + kSsimC2;
+    const float B1 = mx2 + my2 + kSsimC1, B2 = sxx + syy + kSsimC2;
     const float S = (A1 * A2) / (B1 * B2);
     local += S;
     const long long at = (long long)ch * plane + (long long)r * a.Wm + c;
@@ -227,8 +222,6 @@ __global__ __launch_bounds__(kImgBlock) void ssim_backward_kernel(const SsimArgs
   }
 }
 
-int image_launch_status() { return hipGetLastError() == hipSuccess ? RF_OK : RF_ERR_LAUNCH; }
-
 void gaussian_window(float* g) {
   double w[kWin], sum = 0.0;
   for (int k = 0; k < kWin; ++k) {
@@ -298,11 +291,11 @@ int rf_ssim_forward(const RFImage* image, const RFImage* target, int32_t height,
   const long long blocks = (long long)a.tiles_x * a.tiles_y * channels;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(ssim_forward_kernel, dim3((unsigned)blocks), dim3(kImgBlock), 0, st, a);
-  rc = image_launch_status();
+  rc = launch_status();
   if (rc != RF_OK) return rc;
   hipLaunchKernelGGL(ssim_mean_kernel, dim3(1), dim3(kImgBlock), 0, st, (const float*)partials_dev, blocks,
                      (double)a.Hm * (double)a.Wm * (double)channels, mean_dev);
-  return image_launch_status();
+  return launch_status();
 }
 
 int rf_ssim_backward(const RFImage* image, const RFImage* target, int32_t height, int32_t width, int32_t channels, int32_t padding,
@@ -322,7 +315,7 @@ int rf_ssim_backward(const RFImage* image, const RFImage* target, int32_t height
   a.inv_n = (float)(1.0 / ((double)a.Hm * (double)a.Wm * (double)channels));
   const long long blocks = (long long)a.tiles_x * a.tiles_y * channels;
   hipLaunchKernelGGL(ssim_backward_kernel, dim3((unsigned)blocks), dim3(kImgBlock), 0, (hipStream_t)stream, a);
-  return image_launch_status();
+  return launch_status();
 }
 
 }  // extern "C"

@@ -25,17 +25,13 @@
 // Ry Rz, Ry Rz + Rz), evaluated once into LDS.  Output slots inside a workgroup are exclusive prefix sums of the per-thread
 // counts built from wave64 ballots of their bit planes (no atomics), and workgroups write in workgroup order: the output
 // comes out in the canonical order above without a sort, and two extractions are bitwise identical.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "relu_field.h"
+#include "rf_device.h"
 
 namespace {
 
 constexpr int kMeshBlock = 256;  // lattice points per workgroup (4 waves)
 constexpr int kMeshWaves = kMeshBlock / 64;
 constexpr int kRun = kMeshBlock + 1;  // sigma values per run (the +z neighbour of the last point)
-constexpr float kC0 = 0.28209479177387814f;  // degree-0 real SH constant (utils/spherical_harmonics.py)
 
 struct MeshArgs {
   const float* dens;  // reference: densities [.,1] (stride dstride); split / bricked: base [.,4] (stride dstride)
@@ -475,8 +471,6 @@ int mesh_args(const RFGrid* grid, int32_t subdivisions, float iso_level, MeshArg
 
 unsigned int mesh_grid(long long nblocks) { return (unsigned int)(nblocks < (1ll << 20) ? nblocks : (1ll << 20)); }
 
-int mesh_launch_status() { return hipGetLastError() == hipSuccess ? RF_OK : RF_ERR_LAUNCH; }
-
 }  // namespace
 
 extern "C" {
@@ -494,7 +488,7 @@ int rf_mesh_count(const RFGrid* grid, int32_t subdivisions, float iso_level, int
   if (!counts_dev) return RF_ERR_NULL_POINTER;
   hipLaunchKernelGGL(mesh_count_kernel, dim3(mesh_grid(a.nblocks)), dim3(kMeshBlock), 0, (hipStream_t)stream, a,
                      reinterpret_cast<long long*>(counts_dev));
-  return mesh_launch_status();
+  return launch_status();
 }
 
 int rf_mesh_emit(const RFGrid* grid, int32_t subdivisions, float iso_level, const int64_t* offsets_dev, int64_t num_vertices,
@@ -515,7 +509,7 @@ int rf_mesh_emit(const RFGrid* grid, int32_t subdivisions, float iso_level, cons
   o.nrm = normals_dev;
   o.fedge = reinterpret_cast<long long*>(face_edges_dev);
   hipLaunchKernelGGL(mesh_emit_kernel, dim3(mesh_grid(a.nblocks)), dim3(kMeshBlock), 0, (hipStream_t)stream, a, o);
-  return mesh_launch_status();
+  return launch_status();
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// relu_field_kernels.hip -- hand-written CDNA4 (gfx950, wave64) kernels of the ReLU-Fields render path.
+// relu_field_kernels.hip -- hand-written CDNA4 (gfx950, wave64) kernels of the ReLU-Fields render path and training step (shared
+// helpers: rf_device.h; grid utilities, density-only ray walks and ray / point gradients: grid_ / ray_walk_ / ray_grad_kernels.hip).
 //
 // One wavefront renders one ray.  A ray is processed in chunks of 64 samples; each chunk runs three
 // phases that re-shape the wave instead of launching separate kernels:
@@ -20,16 +21,9 @@
 // Reference behaviour being replaced (paths relative to the reference repo):
 //   thre3d_atom/rendering/volumetric/sample.py, process.py, accumulate.py, utils/spherical_harmonics.py,
 //   utils/misc.py:12-50, thre3d_atom/thre3d_reprs/voxels.py:214-331, thre3d_reprs/renderers.py:48-102.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "rf_device.h"
 
 #include <atomic>
-#include <climits>
-#include <cmath>
-#include <cstdlib>
-#include <type_traits>
-
-#include "relu_field.h"
 
 namespace {
 
@@ -46,120 +40,7 @@ namespace {
 #ifndef RF_EMIT_G
 #define RF_EMIT_G 2
 #endif
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
-constexpr float kInfinity = 1e10f;   // thre3d_atom/utils/constants.py:8
-constexpr float kZeroPlus = 1e-10f;  // thre3d_atom/utils/constants.py:7
-
-// real SH constants (utils/spherical_harmonics.py:33-52), rounded to float32 like torch does when a
-// Python float multiplies a float32 tensor
-constexpr float kC0 = 0.28209479177387814f;
-constexpr float kC1 = 0.4886025119029199f;
-constexpr float kC2_0 = 1.0925484305920792f;
-constexpr float kC2_1 = -1.0925484305920792f;
-constexpr float kC2_2 = 0.31539156525252005f;
-constexpr float kC2_3 = -1.0925484305920792f;
-constexpr float kC2_4 = 0.5462742152960396f;
-constexpr float kC3_0 = -0.5900435899266435f;
-constexpr float kC3_1 = 2.890611442640554f;
-constexpr float kC3_2 = -0.4570457994644658f;
-constexpr float kC3_3 = 0.3731763325901154f;
-constexpr float kC3_4 = -0.4570457994644658f;
-constexpr float kC3_5 = 1.445305721320277f;
-constexpr float kC3_6 = -0.5900435899266435f;
-
-struct GridArgs {
-  const float* dens;
-  const float* feat;
-  const uint32_t* occ;
-  int X, Y, Z, F;
-  long long dstride, fstride;
-  float amin[3], amax[3], nscale[3], nbias[3];
-  float rho;
-  int mode;
-  int layout;  // channel arrangement. RF_LAYOUT_REFERENCE: dens[.,1] + feat[.,F];  RF_LAYOUT_SPLIT: dens = base[.,4], feat = rest[.,F-3]
-  // node order: linear (x, y, z) with z fastest, or (RF_LAYOUT_BRICKED) brick-major: 8^3-node bricks stored contiguously,
-  // brick (bx, by, bz) at ((bx * nby + by) * nbz + bz) * 512, node (x & 7, y & 7, z & 7) inside it with z fastest
-  int bricked;
-  int nby, nbz;
-  unsigned int step[3];  // index step to the next node along x, y, z (inside a brick for the bricked order)
-  unsigned int jump[3];  // bricked: step from the last node of a brick to the first node of the next brick on that axis
-  // "near" addressing (host-checked: <= 2^24 nodes, byte strides < 2^24, both tensors inside one 4 GB window that starts at `base`):
-  // a corner's address = uniform 64-bit base (scalar registers) + 32-bit byte offset built with full-rate 24-bit multiplies, instead
-  // of a 64-bit multiply-add per corner -- the gathers of the render kernels are bound by vector-ALU issue, not by memory
-  const char* base;
-  unsigned int dens_off, feat_off;  // byte offsets of dens / feat from base
-  int near32;
-};
-
-// index of node (x, y, z) in the grid tensors (to be multiplied by the tensor's channel stride)
-__device__ __forceinline__ unsigned int node_lin(const GridArgs& g, int x, int y, int z) {
-  if (g.bricked)
-    return (__umul24(__umul24((unsigned)(x >> 3), (unsigned)g.nby) + (unsigned)(y >> 3), (unsigned)g.nbz) + (unsigned)(z >> 3)) * 512u +
-           (unsigned)(((x & 7) << 6) | ((y & 7) << 3) | (z & 7));
-  return __umul24(__umul24((unsigned)x, (unsigned)g.Y) + (unsigned)y, (unsigned)g.Z) + (unsigned)z;
-}
-
-struct RayArgs {
-  const float* origins;
-  const float* directions;
-  long long n;
-  int S;
-  float near, far;
-  const float* tvals;
-  const float* trand;
-  // keyed jitter (RF_FLAG_JITTER_KEYED, trand == NULL): u(ray, sample) = hash of (key, ray0 + ray, sample) -- no [N,S] tensor
-  unsigned long long jkey;
-  long long ray0;  // global index of ray 0 of this batch (jitter stream; pixel index when the camera generates the rays)
-  int jitter;
-  // rays generated in-kernel from a pinhole camera (origins == NULL): ray r = pixel ray0 + r, row-major
-  int cam;
-  int H, W;
-  float focal;
-  float pose[12];  // [3,4] = rotation | translation (camera-to-world)
-};
-
-struct OutArgs {
-  float* colour;
-  float* depth;
-  float* acc;
-  float* disparity;
-  // per-sample cache of the samples that can carry gradient (`need`: inside, T != 0, sigma != 0 under ReLU), COMPACTED per chunk of
-  // 64 samples: the j-th such sample of chunk c of ray r sits at slot r * S + 64 c + j, and bit l of cmask[r][c] says that sample
-  // 64 c + l is one of them -- the adjoint kernels read nothing else (every other sample contributes exactly nothing)
-  float* cache;                // [N,S,4] (raw r, g, b, sigma)
-  float* tcache;               // [N,S] transmittance
-  unsigned long long* cmask;   // [N, ceil(S / 64)]
-  int* stop;                   // [N]
-  // binned backward, fused binning: the forward pass counts, per (brick, flags) key, the samples that will emit a record
-  int* hist;        // [8 * nbricks] or NULL
-  int brick_shift;  // log2 of the brick edge (nodes)
-  int nby, nbz;     // bricks along y and z
-};
-
-struct GradArgs {
-  const float* gcolour;
-  const float* gdepth;
-  const float* gacc;
-  float* gdens;
-  float* gfeat;
-  // emit mode (binned backward): per-sample records instead of a scatter
-  short* keys;      // [N*S] brick id of the sample's cell, kNoBrick for samples without gradient
-  float* records;   // [N*S, 4 * record_quads] the record of every keyed slot (formats: record_quads), in slot order
-  int brick_shift;  // log2 of the brick edge (nodes)
-  int nby, nbz;     // bricks along y and z
-  int* hist;        // [8 * nbricks] records per key, added to (may be NULL)
-  // direct mode (EMIT == 2): expanded records written straight to their final position
-  int* cursor;      // [8 * nbricks] next free position per key
-  float4* sorted;   // [capacity, record_quads(K)]
-  int* hist_clear;  // counters of the forward pass to clear for the next iteration (may be NULL)
-  int nkeys;
-};
-
 constexpr short kNoBrick = -1;  // sorts in front of every (brick, flags) key
-
-
 
 // 16-byte load/store at 4-byte alignment (a corner's 27 features start at a multiple of 108 B)
 struct __attribute__((packed, aligned(4))) f4u {
@@ -202,177 +83,6 @@ __device__ __forceinline__ float4 load_f4(const float4* p) {
 #define RF_NT_CACHE_LOAD 1
 #endif
 
-// ---------------------------------------------------------------------------------------------
-// wave-level helpers (64 lanes)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void wave_lds_fence() {
-  // LDS traffic of one wave is executed in order; this only stops the compiler from moving LDS accesses
-  // across the phase boundary.
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// DPP cross-lane move: lanes without a source (or masked out by ROW_MASK) keep `old`
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_move(float old, float src) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, src),
-                                                               CTRL, ROW_MASK, 0xf, false));
-}
-constexpr int kDppRowShr1 = 0x111, kDppRowShr2 = 0x112, kDppRowShr4 = 0x114, kDppRowShr8 = 0x118;
-constexpr int kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143, kDppWaveShr1 = 0x138, kDppWaveShl1 = 0x130;
-
-// Inclusive prefix of a chunk's transmittance factors E_j = 1 - alpha_j, carried in BOTH forms: e = prod E_j and a = 1 - prod E_j (joined
-// as a' = a_prefix + a e_prefix).  The product alone is as accurate as torch.cumprod's sequential one in the worst case, but not on
-// the rays that matter at high sample counts: with a slowly varying density the factors of neighbouring samples are (nearly) the SAME
-// float, the first doubling step rounds all of them the same way and the later steps multiply that error by 32 per chunk -- coherent
-// over a ray, where the sequential product's roundings are not: 1000 samples of alpha ~ 1e-4 left the transmittance 1e-5 low (accumulated
-// weight of a ray that ends inside the volume 0.99999 instead of 1, depth 6e-5 off: tests/parity_fuzz.py kind "long"; the float32
-// reference is within 1e-6 of the float64 value there).  In the `a` form the same roundings are relative to a ~ 1e-4 .. 1e-2, not to 1.
-// prefix_transmittance() takes 1 - a while a < 1/4 and the product beyond (exact zeros behind an opaque sample stay exact; a ray
-// passes through few chunks in that regime).  DPP (gfx9): 4 row_shr steps inside each row of 16 lanes, then row_bcast:15 / :31 to fold
-// the rows; 24 VALU instructions per chunk (the product alone took 6), no LDS traffic.
-__device__ __forceinline__ void wave_incl_scan_trans(float& e, float& a) {
-  auto step = [&](auto ctrl_tag, auto mask_tag) {
-    constexpr int CTRL = decltype(ctrl_tag)::value, MASK = decltype(mask_tag)::value;
-    const float ep = dpp_move<CTRL, MASK>(1.0f, e), ap = dpp_move<CTRL, MASK>(0.0f, a);
-    a = __builtin_fmaf(a, ep, ap);
-    e = e * ep;
-  };
-  step(std::integral_constant<int, kDppRowShr1>{}, std::integral_constant<int, 0xf>{});
-  step(std::integral_constant<int, kDppRowShr2>{}, std::integral_constant<int, 0xf>{});
-  step(std::integral_constant<int, kDppRowShr4>{}, std::integral_constant<int, 0xf>{});
-  step(std::integral_constant<int, kDppRowShr8>{}, std::integral_constant<int, 0xf>{});
-  step(std::integral_constant<int, kDppRowBcast15>{}, std::integral_constant<int, 0xa>{});
-  step(std::integral_constant<int, kDppRowBcast31>{}, std::integral_constant<int, 0xc>{});
-}
-__device__ __forceinline__ float prefix_transmittance(float e, float a) { return (a < 0.25f) ? 1.0f - a : e; }
-
-__device__ __forceinline__ float read_lane(float x, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), lane));
-}
-
-// inclusive SUFFIX sum: result[lane] = sum_{l >= lane} x[l]
-__device__ __forceinline__ float wave_incl_rscan_add(float x, int lane) {
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    float y = __shfl_down(x, off, kWave);
-    if (lane + off < kWave) x = x + y;
-  }
-  return x;
-}
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) x += __shfl_xor(x, off, kWave);
-  return x;
-}
-
-// exp / sigmoid on the hardware transcendental units (v_exp_f32 is 2^x, v_rcp_f32; ~1 ulp each).  The reference's
-// own CPU (SLEEF) and GPU (libdevice) paths differ from each other by as much; the parity bar is 1e-5.
-__device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float sigmoidf_(float x) { return __builtin_amdgcn_rcpf(1.0f + exp_fast(-x)); }
-// alpha = 1 - exp(-x), x = sigma * delta (density2occupancy_pb, accumulate.py:24-28; x < 0 only under Identity/Identity densities, where
-// alpha < 0 and the transmittance grows above 1), the way the REFERENCE's float32 arithmetic
-// produces it: E = exp(-x) correctly rounded, alpha = 1 - E (an exact subtraction: alpha is a multiple of 2^-24 and 1 - alpha == E, so
-// that weights alpha_i T_i and transmittances T_i E_i telescope without a bias).  v_exp_f32 is a one-ulp exponential: at the small x of
-// densely sampled rays (1000+ samples: x ~ 1e-3) its errors in E near 1 showed as 3..8e-5 on depth at 4000 .. 5000 samples per ray, where the
-// float32 reference stays within 2e-6 of the float64 value (tests/parity_fuzz.py, kind "long").  Below 1/16: E = 1 - (x - x^2/2 + ... ),
-// the series to 2e-9 relative, i.e. the correctly rounded exponential in all but a handful of cases.  (alpha taken from the series
-// itself is MORE accurate than the reference's -- and then 1 - alpha is rounded, with the same sign sample after sample where the
-// density varies slowly: accumulated weights of opaque rays came out 1.5e-5 short of 1.  Measured, not kept.)  The series is taken for
-// |x| < 1/16 only: truncated, it falls away from exp(-x) fast on the negative side (1.4e-5 relative at x = -0.5, 0.93 at x = -10), and
-// exp_fast is right for either sign (+inf for a negative density over the last sample's 1e10-long interval, as in the reference).
-__device__ __forceinline__ float occupancy_alpha(float x, float& E) {
-  float t = __builtin_fmaf(-x, 1.0f / 120.0f, 1.0f / 24.0f);
-  t = __builtin_fmaf(-x, t, 1.0f / 6.0f);
-  t = __builtin_fmaf(-x, t, 0.5f);
-  t = __builtin_fmaf(-x, t, 1.0f);
-  const float big = exp_fast(-x);
-  E = (__builtin_fabsf(x) < 0.0625f) ? __builtin_fmaf(-x, t, 1.0f) : big;
-  return 1.0f - E;
-}
-// softplus'(x) = sigmoid(x) = 1 - exp(-softplus(x)), from the cached activated density s = softplus(x) >= 0, to RELATIVE accuracy: a
-// sample far below the surface has s ~ 1e-9 and 1 - exp(-s) cancels to 0 in float32, but the last sample of a ray carries
-// delta = 1e10 |d| (accumulate.py:49-52), so its d alpha / d sigma is ~1e10 and the product is an ordinary gradient that the reference
-// (ATen's softplus backward: z / (z + 1), z = exp(x)) gets right.  Below 0.25 the alternating series, six terms (next term / s < 5e-8).
-__device__ __forceinline__ float softplus_slope(float s) {
-  if (s < 0.25f) return s * (1.0f - s * (0.5f - s * (1.0f / 6.0f - s * (1.0f / 24.0f - s * (1.0f / 120.0f - s * (1.0f / 720.0f))))));
-  return 1.0f - exp_fast(-s);
-}
-
-// ---------------------------------------------------------------------------------------------
-// sampling (rendering/volumetric/sample.py:39-68)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float z_uniform(float near, float far, float t) { return near * (1.0f - t) + far * t; }
-
-// jitter u in [0, 1) of sample s, or no jitter at all (have_u = false)
-__device__ __forceinline__ float z_sample(const float* __restrict__ tv, bool have_u, float u, int s, int S, float near, float far) {
-  const float zc = z_uniform(near, far, tv[s]);
-  if (!have_u) return zc;
-  // stratified jitter: lower/upper = neighbouring mid-points (sample.py:57-64).  (The neighbours are loaded unconditionally, with
-  // clamped indices: a load under a lane condition is merged with a copy, and the copy waits for the load on the spot.)
-  const float zm = z_uniform(near, far, tv[s > 0 ? s - 1 : 0]), zp = z_uniform(near, far, tv[s < S - 1 ? s + 1 : S - 1]);
-  const float lo = (s > 0) ? 0.5f * (zc + zm) : zc;
-  const float hi = (s < S - 1) ? 0.5f * (zp + zc) : zc;
-  return lo + (hi - lo) * u;
-}
-
-// slab test of sample.py:71-184; returns true when the ray hits, writes the (clamped) bounds either way
-__device__ __forceinline__ bool ray_box(const float o[3], const float d[3], const float bmin[3], const float bmax[3],
-                                        float near, float far, float& t0, float& t1) {
-  float lo_run = 0.f, hi_run = 0.f;
-  bool hit = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float den = d[a] + kZeroPlus;
-    const float ta = (bmin[a] - o[a]) / den;
-    const float tb = (bmax[a] - o[a]) / den;
-    const bool swap = ta > tb;
-    const float lo = swap ? tb : ta;
-    const float hi = swap ? ta : tb;
-    if (a == 0) {
-      lo_run = lo;
-      hi_run = hi;
-    } else {
-      hit = hit && !((lo_run > hi) || (lo > hi_run));
-      lo_run = (lo > lo_run) ? lo : lo_run;
-      hi_run = (hi < hi_run) ? hi : hi_run;
-    }
-  }
-  t0 = hit ? lo_run : near;
-  t1 = hit ? hi_run : far;
-  t0 = (t0 < 0.f) ? 0.f : t0;  // torch.clip(min=0): NaN stays NaN, like the reference
-  t1 = (t1 < 0.f) ? 0.f : t1;
-  return hit;
-}
-
-// ---------------------------------------------------------------------------------------------
-// per-sample geometry (voxels.py:214-223 normalise, GridSampler.h:27-36 un-normalise)
-// ---------------------------------------------------------------------------------------------
-struct Cell {
-  float idx[3];  // continuous index ((q + 1) * size - 1) / 2
-  int i0[3];     // floor of the continuous index (may be -1)
-  float w0[3];   // weight of the lower node along each axis  = (i0 + 1) - idx
-  float w1[3];   // weight of the upper node                   = idx - i0
-};
-
-__device__ __forceinline__ Cell locate(const float p[3], const GridArgs& g) {
-  Cell c;
-  const int dims[3] = {g.X, g.Y, g.Z};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float q = p[a] * g.nscale[a] + g.nbias[a];
-    const float idx = ((q + 1.0f) * (float)dims[a] - 1.0f) / 2.0f;
-    const float fl = floorf(idx);
-    c.idx[a] = idx;
-    c.i0[a] = (int)fl;
-    c.w1[a] = idx - fl;
-    c.w0[a] = (fl + 1.0f) - idx;
-  }
-  return c;
-}
-
 // LDS work-list entries, 12 dwords each.
 // forward:  [0..1] linear voxel index of the (clamped) corner 000   [2] sample lane | step bits << 8
 //           [3] unused   [4..11] the 8 trilinear corner weights (0 for corners outside the grid)
@@ -381,248 +91,6 @@ __device__ __forceinline__ Cell locate(const float p[3], const GridArgs& g) {
 //           [2..7] w0x w1x w0y w1y w0z w1z   [8..11] dL/d(pre-activation density), dL/d(raw r, g, b)
 constexpr int kEntryFwd = 12;
 constexpr int kEntryBwd = 12;
-
-__device__ __forceinline__ uint32_t pack_cell(const Cell& c) {
-  return (uint32_t)(c.i0[0] + 1) | ((uint32_t)(c.i0[1] + 1) << 11) | ((uint32_t)(c.i0[2] + 1) << 22);
-}
-
-struct Corners {
-  unsigned int lin[8];  // linear voxel index of the (clamped) corner k = dx + 2 dy + 4 dz
-  unsigned int s[3];    // index steps from corner 000 to its x / y / z upper neighbour (0 where clamping collapses them)
-  float w[8];           // trilinear weight, forced to 0 for corners outside the grid
-};
-
-// grid dims <= 2046, so every product below has 24-bit operands (v_mul_u32_u24 runs at full rate, v_mul_lo_u32 does
-// not); voxel counts are limited to 2^32 / stride by the host-side check.
-__device__ __forceinline__ Corners corners_of(uint32_t packed, const float wts[6], const GridArgs& g) {
-  const int ix0 = (int)(packed & 0x7ffu) - 1, iy0 = (int)((packed >> 11) & 0x7ffu) - 1, iz0 = (int)(packed >> 22) - 1;
-  const bool okx[2] = {ix0 >= 0, ix0 + 1 < g.X};  // the point is inside the box: ix0 in [-1, X-1]
-  const bool oky[2] = {iy0 >= 0, iy0 + 1 < g.Y};
-  const bool okz[2] = {iz0 >= 0, iz0 + 1 < g.Z};
-  const int cx0 = max(ix0, 0), cy0 = max(iy0, 0), cz0 = max(iz0, 0);
-  const unsigned int lin0 = node_lin(g, cx0, cy0, cz0);
-  // step to the upper node: a whole voxel (a jump into the next brick when the lower node is a brick's last one), or 0
-  // when the clamped upper node coincides with the lower one
-  const unsigned int sx = (okx[0] && okx[1]) ? ((g.bricked && (cx0 & 7) == 7) ? g.jump[0] : g.step[0]) : 0u;
-  const unsigned int sy = (oky[0] && oky[1]) ? ((g.bricked && (cy0 & 7) == 7) ? g.jump[1] : g.step[1]) : 0u;
-  const unsigned int sz = (okz[0] && okz[1]) ? ((g.bricked && (cz0 & 7) == 7) ? g.jump[2] : g.step[2]) : 0u;
-  // (a node outside the grid gets weight 0: masked per axis -- 0 times the finite weights of the other axes is the same +0)
-  const float ax[2] = {okx[0] ? wts[0] : 0.0f, okx[1] ? wts[1] : 0.0f};
-  const float ay[2] = {oky[0] ? wts[2] : 0.0f, oky[1] ? wts[3] : 0.0f};
-  const float az[2] = {okz[0] ? wts[4] : 0.0f, okz[1] ? wts[5] : 0.0f};
-  const float wxy[4] = {ax[0] * ay[0], ax[1] * ay[0], ax[0] * ay[1], ax[1] * ay[1]};  // [dx + 2 dy]
-  Corners c;
-  c.s[0] = sx;
-  c.s[1] = sy;
-  c.s[2] = sz;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-    c.lin[k] = lin0 + (dx ? sx : 0u) + (dy ? sy : 0u) + (dz ? sz : 0u);
-    c.w[k] = wxy[dx + 2 * dy] * az[dz];
-  }
-  return c;
-}
-
-__device__ __forceinline__ float density_post(float pre, int mode);
-
-// density: post( interp( pre(D * rho) ) )  (voxels.py:292-309)
-// (interp_density_values, further down, is this function handing back the 8 corner values: a change here is a change there, or
-// rf_render_geometry's weights stop being the forward's bits)
-__device__ __forceinline__ float interp_density(const Corners& c, const GridArgs& g, float& pre_out) {
-  float raw[8];
-  if (g.near32) {  // (wave-uniform)
-    const unsigned int sb = (unsigned int)g.dstride * 4u;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned int o = __umul24(c.lin[k], sb);
-      raw[k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(g.dens) + (size_t)o);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) raw[k] = g.dens[c.lin[k] * g.dstride];
-    asm volatile("" ::: "memory");  // (keeps the two branches' loads apart: merged, they lose the scalar-base addressing)
-  }
-  float acc = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    float v = raw[k] * g.rho;
-    if (g.mode == RF_DENSITY_ABS) v = fabsf(v);
-    acc = acc + v * c.w[k];
-  }
-  pre_out = acc;
-  if (g.mode == RF_DENSITY_RELU) return fmaxf(acc, 0.0f);
-  if (g.mode == RF_DENSITY_SOFTPLUS) return (acc > 20.0f) ? acc : log1pf(expf(acc));
-  return acc;
-}
-
-// signed SH basis in the reference's operation order (utils/spherical_harmonics.py:86-116)
-template <int K>
-__device__ __forceinline__ void sh_basis(float x, float y, float z, float Y[16]) {
-  Y[0] = kC0;
-  if (K > 1) {
-    Y[1] = -(kC1 * y);
-    Y[2] = kC1 * z;
-    Y[3] = -(kC1 * x);
-  }
-  if (K > 4) {
-    const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-    Y[4] = kC2_0 * xy;
-    Y[5] = kC2_1 * yz;
-    Y[6] = kC2_2 * ((2.0f * zz - xx) - yy);
-    Y[7] = kC2_3 * xz;
-    Y[8] = kC2_4 * (xx - yy);
-    if (K > 9) {
-      Y[9] = (kC3_0 * y) * (3.0f * xx - yy);
-      Y[10] = (kC3_1 * xy) * z;
-      Y[11] = (kC3_2 * y) * ((4.0f * zz - xx) - yy);
-      Y[12] = (kC3_3 * z) * ((2.0f * zz - 3.0f * xx) - 3.0f * yy);
-      Y[13] = (kC3_4 * x) * ((4.0f * zz - xx) - yy);
-      Y[14] = (kC3_5 * z) * (xx - yy);
-      Y[15] = (kC3_6 * x) * (xx - 3.0f * yy);
-    }
-  }
-}
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-  x ^= x >> 16;
-  x *= 0x7feb352dU;
-  x ^= x >> 15;
-  x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-
-// Keyed jitter of the stratified sampler (sample.py:57-64 draws torch.rand(N, S)): a counter-based generator instead of a
-// [N, S] tensor.  u = 24 random bits of mix32 over (per-ray seed, sample index); the per-ray seed hashes the 64-bit key with
-// the global ray index.  Restated in oracle/relu_field_oracle.py:keyed_jitter (tests compare the two bit for bit).
-__device__ __forceinline__ uint32_t jitter_ray_seed(unsigned long long key, long long gray) {
-  const uint32_t a = mix32((uint32_t)gray ^ (uint32_t)key);
-  const uint32_t b = mix32((uint32_t)((unsigned long long)gray >> 32) + (uint32_t)(key >> 32));
-  return a ^ (b * 0x9E3779B9u + 0x85EBCA6Bu);
-}
-__device__ __forceinline__ float jitter_uniform(uint32_t ray_seed, int s) {
-  const uint32_t h = mix32(ray_seed + (uint32_t)s * 0x9E3779B9u);
-  return (float)(h >> 8) * 5.9604644775390625e-08f;  // [0, 1) on the 2^-24 lattice
-}
-
-__device__ __forceinline__ void pixel_ray(int i, int j, int H, int W, float focal, const float* R, float d[3]) {
-  // pixel centres; camera looks along -z, y up
-  const float cx = (((float)j + 0.5f) - (float)W * 0.5f) / focal;
-  const float cy = -((((float)i + 0.5f) - (float)H * 0.5f) / focal);
-  const float cz = -1.0f;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) d[a] = (R[a * 3 + 0] * cx + R[a * 3 + 1] * cy) + R[a * 3 + 2] * cz;
-}
-
-// ---------------------------------------------------------------------------------------------
-// per-ray state shared by forward and backward
-// ---------------------------------------------------------------------------------------------
-struct RayState {
-  float o[3], d[3];
-  float dnorm;
-  float near, far;
-  uint32_t jseed;  // keyed jitter: per-ray seed
-};
-
-__device__ __forceinline__ RayState load_ray(const RayArgs& r, const GridArgs& g, long long ray, uint32_t flags) {
-  RayState st;
-  if (r.cam) {  // cast_rays (utils/misc.py:12-50) fused: pixel p = ray0 + ray, row-major
-    const long long pidx = r.ray0 + ray;
-    const int i = (int)(pidx / r.W), j = (int)(pidx - (long long)i * r.W);
-    const float R[9] = {r.pose[0], r.pose[1], r.pose[2], r.pose[4], r.pose[5], r.pose[6], r.pose[8], r.pose[9], r.pose[10]};
-    pixel_ray(i, j, r.H, r.W, r.focal, R, st.d);
-    st.o[0] = r.pose[3];
-    st.o[1] = r.pose[7];
-    st.o[2] = r.pose[11];
-  } else {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      st.o[a] = r.origins[ray * 3 + a];
-      st.d[a] = r.directions[ray * 3 + a];
-    }
-  }
-  st.jseed = r.jitter ? jitter_ray_seed(r.jkey, r.ray0 + ray) : 0u;
-  st.dnorm = sqrtf((st.d[0] * st.d[0] + st.d[1] * st.d[1]) + st.d[2] * st.d[2]);
-  st.near = r.near;
-  st.far = r.far;
-  if (flags & RF_FLAG_AABB_SAMPLING) {
-    float t0, t1;
-    ray_box(st.o, st.d, g.amin, g.amax, r.near, r.far, t0, t1);
-    st.near = t0;
-    st.far = t1;
-  }
-  return st;
-}
-
-// everything P0 knows about one sample
-struct Sample {
-  float z, delta;
-  bool valid, inside;
-  Cell cell;
-};
-
-// the sample of lane-index s given its ray parameter z and the next sample's parameter z_next
-__device__ __forceinline__ Sample sample_at(const RayState& st, const RayArgs& r, const GridArgs& g, int s, float z,
-                                            float z_next) {
-  Sample sm;
-  sm.valid = s < r.S;
-  sm.z = z;
-  sm.delta = (s < r.S - 1) ? (z_next - z) * st.dnorm : kInfinity * st.dnorm;  // accumulate.py:50-55
-  float p[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) p[a] = st.o[a] + st.d[a] * sm.z;
-  sm.inside = sm.valid && p[0] > g.amin[0] && p[0] < g.amax[0] && p[1] > g.amin[1] && p[1] < g.amax[1] &&
-              p[2] > g.amin[2] && p[2] < g.amax[2];  // strict, voxels.py:252-274
-  sm.cell = locate(p, g);
-  return sm;
-}
-
-__device__ __forceinline__ float z_of(const RayState& st, const RayArgs& r, long long ray, int s) {
-  const int sc = min(s, r.S - 1);
-  float u = 0.0f;
-  if (r.trand)
-    u = r.trand[ray * (long long)r.S + sc];
-  else if (r.jitter)
-    u = jitter_uniform(st.jseed, sc);
-  return z_sample(r.tvals, r.trand != nullptr || r.jitter, u, sc, r.S, st.near, st.far);
-}
-
-// z_of in two halves, for kernels that want every load of several samples in flight before the first one is used:
-// z_requests issues the (unconditional, clamped) t_vals reads, z_from does z_of's arithmetic on them -- bit for bit the same value.
-struct ZRequests {
-  float t0, tm, tp;
-};
-__device__ __forceinline__ ZRequests z_requests(const RayArgs& r, int s) {
-  const int sc = min(s, r.S - 1);
-  ZRequests q;
-  q.t0 = r.tvals[sc];
-  q.tm = r.tvals[sc > 0 ? sc - 1 : 0];
-  q.tp = r.tvals[sc < r.S - 1 ? sc + 1 : r.S - 1];
-  return q;
-}
-// (a jitter TABLE, if one is used instead of the keyed generator, is read here, synchronously)
-__device__ __forceinline__ float z_from(const RayState& st, const RayArgs& r, const ZRequests& q, long long ray, int s) {
-  const int sc = min(s, r.S - 1);
-  const float zc = z_uniform(st.near, st.far, q.t0);
-  if (!(r.trand != nullptr || r.jitter)) return zc;
-  const float u = r.trand ? r.trand[ray * (long long)r.S + sc] : jitter_uniform(st.jseed, sc);
-  const float zm = z_uniform(st.near, st.far, q.tm), zp = z_uniform(st.near, st.far, q.tp);
-  const float lo = (sc > 0) ? 0.5f * (zc + zm) : zc;
-  const float hi = (sc < r.S - 1) ? 0.5f * (zp + zc) : zc;
-  return lo + (hi - lo) * u;
-}
-
-__device__ __forceinline__ Sample make_sample(const RayState& st, const RayArgs& r, const GridArgs& g, long long ray,
-                                              int s) {
-  return sample_at(st, r, g, s, z_of(st, r, ray, s), z_of(st, r, ray, s + 1));
-}
-
-__device__ __forceinline__ bool cell_occupied(const Cell& c, const GridArgs& g) {
-  // bit index over the (X+1)(Y+1)(Z+1) cells whose lower node is i0 in [-1, dim-1]
-  const long long bit = ((long long)(c.i0[0] + 1) * (g.Y + 1) + (c.i0[1] + 1)) * (g.Z + 1) + (c.i0[2] + 1);
-  return (g.occ[bit >> 5] >> (bit & 31)) & 1u;
-}
 
 // ---------------------------------------------------------------------------------------------
 // feature gather for LPS lanes per sample (P1).  Returns raw RGB in every lane of the group.
@@ -647,7 +115,6 @@ __device__ __forceinline__ float group_sum_to_last(float x) {
   x += dpp_move<kDppRowShr1, 0xf>(0.0f, x);
   return x;
 }
-
 
 // What one P1 lane gathers: 4 consecutive floats at `src + voxel * stride + off` of every corner, and for each of
 // the 4 elements which colour it feeds (chan, -1 = not owned) with which SH weight (yb).
@@ -832,39 +299,6 @@ __device__ __forceinline__ int brick_key(const int i0[3], const GridArgs& g, int
   return (int)((__umul24(__umul24((unsigned)((b3[0] << 1) | f3[0]), (unsigned)nby) + (unsigned)b3[1], (unsigned)nbz) + (unsigned)b3[2]) << 2) | f3[1] | (f3[2] << 1);
 }
 
-// Parameter interval of a ray inside the box (same slab test as the AABB sampler, reciprocal-based: only used with a generous
-// margin, never for sample positions).  A chunk of 64 samples that lies outside it by that margin contributes exactly
-// nothing -- sigma = 0 -> alpha = 0 -> w = 0, T unchanged, no gradient -- and is skipped without evaluating a single sample.
-struct BoxSpan {
-  float t_in, t_out, zpad, margin;
-  bool hits;
-};
-
-__device__ __forceinline__ BoxSpan box_span(const RayState& st, const RayArgs& r, const GridArgs& g) {
-  BoxSpan b;
-  b.t_in = -kInfinity;
-  b.t_out = kInfinity;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float inv = __builtin_amdgcn_rcpf(st.d[a] + kZeroPlus);
-    const float ta = (g.amin[a] - st.o[a]) * inv, tb = (g.amax[a] - st.o[a]) * inv;
-    b.t_in = fmaxf(b.t_in, fminf(ta, tb));
-    b.t_out = fminf(b.t_out, fmaxf(ta, tb));
-  }
-  b.margin = 1e-3f * (1.0f + fabsf(b.t_in) + fabsf(b.t_out));
-  b.hits = b.t_out >= b.t_in - b.margin;
-  b.zpad = fabsf(st.far - st.near) / (float)(r.S > 1 ? r.S - 1 : 1);  // jitter stays within one stratum
-  return b;
-}
-
-// wave-uniform: no sample of chunk `chunk` can be inside the box
-__device__ __forceinline__ bool chunk_outside_box(const BoxSpan& b, const RayState& st, const RayArgs& r, int chunk) {
-  const int s_first = chunk * kWave, s_last = min(r.S - 1, chunk * kWave + kWave - 1);
-  const float za = z_uniform(st.near, st.far, r.tvals[s_first]), zb = z_uniform(st.near, st.far, r.tvals[s_last]);
-  const float zlo = fminf(za, zb) - b.zpad, zhi = fmaxf(za, zb) + b.zpad;
-  return !b.hits || zhi < b.t_in - b.margin || zlo > b.t_out + b.margin;
-}
-
 // =============================================================================================
 // forward
 // =============================================================================================
@@ -995,15 +429,9 @@ __device__ __forceinline__ void render_forward_ray(const GridArgs& g, const RayA
         sigma = interp_density(cn, g, pre);
       }
     }
-    float one_minus;  // = exp(-sigma delta) = 1 - alpha exactly
-    const float alpha = occupancy_alpha(sigma * sm.delta, one_minus);  // density2occupancy_pb, accumulate.py:24-28
-    float incl_e = sm.valid ? one_minus : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
-    wave_incl_scan_trans(incl_e, incl_a);
-    const float incl = prefix_transmittance(incl_e, incl_a);
-    const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
-    const float T = T_carry * excl;
-    const float w = alpha * T;
-    T_carry = T_carry * read_lane(incl, kWave - 1);
+    const ChunkWeights cw = chunk_weights(sigma, sm.delta, sm.valid, T_carry);
+    const float T = cw.T, w = cw.alpha * T;
+    T_carry = T_carry * read_lane(cw.incl, kWave - 1);
     processed = min(r.S, (chunk + 1) * kWave);
 
     // a sample needs its colour only if it can contribute: inside, T != 0 and (under ReLU) sigma != 0
@@ -1700,27 +1128,6 @@ __global__ __launch_bounds__(kWave * WPB, (K == 16 ? 2 : RF_TILE_WAVES)) void re
   }
 }
 
-// The cached samples of a chunk (forward pass, SAVE): lane l of the adjoint handles sample 64 c + l like the forward pass did; its
-// cache entry, if bit l of the chunk's mask is set, is entry rank(l) = popcount(mask below l) of the chunk's slots.  Lanes without
-// an entry load entry 0 of the chunk (a line the wave touches anyway; a load under a lane condition would be followed by a
-// register merge that waits for it) and are zeroed by the caller.
-struct CachedSample {
-  float4 cv;  // raw r, g, b, sigma
-  float T;
-};
-__device__ __forceinline__ long long cached_slot(long long ray, int S, int chunk, unsigned long long cm, int lane) {
-  const bool has = (cm >> lane) & 1ull;
-  const int rank = __popcll(cm & ((1ull << lane) - 1ull));
-  return ray * (long long)S + chunk * kWave + (has ? rank : 0);
-}
-// wave-uniform mask of chunk `chunk` out of the per-lane copies (lane c holds chunk 64 g + c)
-__device__ __forceinline__ unsigned long long chunk_mask_of(unsigned long long lanes_masks, int chunk) {
-  const int c = chunk & (kWave - 1);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)lanes_masks, c);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(lanes_masks >> 32), c);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 // lanes per corner for the backward scatter: F features + 1 density, rounded up to a power of two
 template <int K, bool DIFFUSE>
 struct ScatterLayout {
@@ -1898,13 +1305,7 @@ __global__ __launch_bounds__(kBlock) void render_backward_kernel(GridArgs g, Ray
     suffix += __shfl(incl, 0, kWave);
 
     float g_sigma = sm.delta * (Tn * e - after);
-    float g_pre;
-    if (g.mode == RF_DENSITY_RELU)
-      g_pre = (sigma > 0.0f) ? g_sigma : 0.0f;
-    else if (g.mode == RF_DENSITY_SOFTPLUS)
-      g_pre = g_sigma * softplus_slope(sigma);
-    else
-      g_pre = g_sigma;
+    float g_pre = density_pre_grad(g_sigma, sigma, g.mode);
     float g_raw[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) g_raw[ch] = (w * gC[ch]) * (c[ch] * (1.0f - c[ch]));
@@ -2144,13 +1545,7 @@ __device__ __forceinline__ void render_emit_direct_ray(const GridArgs& g, const 
       const float after = (incl - we) + suffix;  // sum over samples strictly behind this one
       suffix += __shfl(incl, 0, kWave);
       const float g_sigma = dl[u] * (Tn * e - after);
-      float g_pre;
-      if (g.mode == RF_DENSITY_RELU)
-        g_pre = (sigma > 0.0f) ? g_sigma : 0.0f;
-      else if (g.mode == RF_DENSITY_SOFTPLUS)
-        g_pre = g_sigma * softplus_slope(sigma);
-      else
-        g_pre = g_sigma;
+      float g_pre = density_pre_grad(g_sigma, sigma, g.mode);
       const int pos = __shfl(base_[u], hl_[u]) + (lane - hl_[u]);
       if (have) {
         // (a counted sample is inside the box; its record is written even when its gradient happens to vanish)
@@ -2290,8 +1685,6 @@ struct BrickArgs {
   float* partial;          // [num_bricks][parts][brick_acc_words] partial accumulator images
   int* part_state;         // [num_bricks][1 + parts]: arrival counter, then one "wrote an image" flag per part; all zero between launches
 };
-
-
 
 // Sorted position p (>= *begin: the slots without gradient sort in front) receives the record of slot perm[p] (Q quads each;
 // one thread per quad, coalesced 16-byte stores).
@@ -3449,734 +2842,12 @@ __global__ __launch_bounds__(BX == 4 ? kBrickThreads / 2 : kBrickThreads, (K > 9
 }
 
 // =============================================================================================
-// stage transition: scale_voxel_grid_with_required_output_size (thre3d_reprs/voxels.py:334-373) = F.interpolate(mode="trilinear",
-// align_corners=False) of the [F+1]-channel volume.  One thread per (destination node, channel), channel fastest; source and
-// destination in any storage (the value lands in the destination's layout directly: no unified tensor, no permutes).  ATen's
-// arithmetic (UpSampleKernel.cpp / UpSample.h): scale = in / out in float, src = fma(scale, dst + 0.5, -0.5) clamped at 0,
-// i0 = min(floor(src), in - 1), i1 = i0 + (i0 < in - 1), lambda = clamp(src - i0, 0, 1); the 8 corners weighted by the products of
-// the per-axis weights and summed in the order of ATen's channels-last CPU kernel (see below).
-// =============================================================================================
-__device__ __forceinline__ long long channel_offset(const GridArgs& g, unsigned int lin, int ch, int K, bool& in_first) {
-  // ch: 0 = density, 1..3 = degree-0 coefficient of r, g, b, then colour-major higher degrees (the order of a node's accumulators)
-  if (g.layout == RF_LAYOUT_REFERENCE) {
-    in_first = ch == 0;
-    if (ch == 0) return (long long)lin * g.dstride;
-    if (ch < 4) return (long long)lin * g.fstride + (long long)(ch - 1) * K;
-    const int j = ch - 4, colour = j / (K - 1), kk = 1 + j - colour * (K - 1);
-    return (long long)lin * g.fstride + (long long)colour * K + kk;
-  }
-  in_first = ch < 4;
-  return ch < 4 ? (long long)lin * g.dstride + ch : (long long)lin * g.fstride + (ch - 4);
-}
-
-struct UpsampleAxis {
-  int i0, i1;
-  float w0, w1;
-};
-__device__ __forceinline__ UpsampleAxis upsample_axis(int dst, int in_size, float scale) {
-  float src = fmaf(scale, (float)dst + 0.5f, -0.5f);  // (contracted in ATen's build)
-  src = src < 0.0f ? 0.0f : src;
-  UpsampleAxis a;
-  a.i0 = min((int)floorf(src), in_size - 1);
-  a.i1 = a.i0 + (a.i0 < in_size - 1 ? 1 : 0);
-  const float lambda = fminf(fmaxf(src - (float)a.i0, 0.0f), 1.0f);
-  a.w0 = 1.0f - lambda;
-  a.w1 = lambda;
-  return a;
-}
-
-__global__ void upsample_grid_kernel(GridArgs src, GridArgs dst, float* dst_first, float* dst_second, long long total) {
-  const int C = dst.F + 1, K = dst.F / 3;
-  const float sx = (float)src.X / (float)dst.X, sy = (float)src.Y / (float)dst.Y, sz = (float)src.Z / (float)dst.Z;
-  for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
-    const int ch = (int)(it % C);
-    long long node = it / C;
-    const int z = (int)(node % dst.Z);
-    node /= dst.Z;
-    const int y = (int)(node % dst.Y), x = (int)(node / dst.Y);
-    const UpsampleAxis ax = upsample_axis(x, src.X, sx), ay = upsample_axis(y, src.Y, sy), az = upsample_axis(z, src.Z, sz);
-    auto at = [&](int xi, int yi, int zi) -> float {
-      bool first;
-      const long long off = channel_offset(src, node_lin(src, xi, yi, zi), ch, K, first);
-      return (first ? src.dens : src.feat)[off];
-    };
-    // corner k = (dx, dy, dz) with z fastest, weight = (wx * wy) * wz
-    float val[8], wgt[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int dx = k >> 2, dy = (k >> 1) & 1, dz = k & 1;
-      val[k] = at(dx ? ax.i1 : ax.i0, dy ? ay.i1 : ay.i0, dz ? az.i1 : az.i0);
-      wgt[k] = ((dx ? ax.w1 : ax.w0) * (dy ? ay.w1 : ay.w0)) * (dz ? az.w1 : az.w0);
-    }
-    // The reference hands F.interpolate a channels-last volume (features in the reference order, density last), and ATen's
-    // channels-last CPU kernel sums the 8 weighted corners right to left in its 8-wide vector body and left to right in the
-    // scalar tail of the last C mod 8 channels, every step contracted to a fused multiply-add.  Both orders are reproduced per
-    // channel, so that the result equals the reference's own output bit for bit (golden G3).
-    int uc;  // index of this channel in the reference's unified [features, density] order
-    if (ch == 0) {
-      uc = dst.F;
-    } else if (ch < 4) {
-      uc = (ch - 1) * K;
-    } else {
-      const int j = ch - 4, colour = j / (K - 1);
-      uc = colour * K + 1 + (j - colour * (K - 1));
-    }
-    float v;
-    if (uc < (C & ~7)) {
-      v = fmaf(val[7], wgt[7], val[6] * wgt[6]);
-#pragma unroll
-      for (int k = 5; k >= 0; --k) v = fmaf(val[k], wgt[k], v);
-    } else {
-      v = fmaf(val[0], wgt[0], val[1] * wgt[1]);
-#pragma unroll
-      for (int k = 2; k < 8; ++k) v = fmaf(val[k], wgt[k], v);
-    }
-    bool first;
-    const long long off = channel_offset(dst, node_lin(dst, x, y, z), ch, K, first);
-    (first ? dst_first : dst_second)[off] = v;
-  }
-}
-
-// Re-layout of a whole grid: every (node, channel) of `src` copied to where `dst`'s storage keeps it (same dims, same F).  One
-// thread per element, channel fastest.  Used to keep a split-layout SHADOW of a grid held in the reference's two tensors: the
-// forward passes gather from the shadow (aligned 16-byte base records, density and degree-0 colour in one gather), the
-// gradients are produced in the layout of the Parameters.
-__global__ void convert_grid_kernel(GridArgs src, GridArgs dst, float* dst_first, float* dst_second, unsigned int nodes) {
-  // threadIdx.x = channel (32 or 64 lanes per node, the ones beyond F + 1 idle), threadIdx.y = node within the block: no
-  // division for the channel, 32-bit index arithmetic throughout (node counts are < 2^32)
-  const int C = dst.F + 1, K = dst.F / 3;
-  const int ch = threadIdx.x;
-  const bool linear = !src.bricked && !dst.bricked;  // node index = linear index in both
-  for (unsigned int node = blockIdx.x * blockDim.y + threadIdx.y; node < nodes; node += gridDim.x * blockDim.y) {
-    if (ch >= C) continue;
-    unsigned int ls = node, ld = node;
-    if (!linear) {
-      const unsigned int z = node % (unsigned)dst.Z, t = node / (unsigned)dst.Z;
-      const unsigned int y = t % (unsigned)dst.Y, x = t / (unsigned)dst.Y;
-      ls = node_lin(src, (int)x, (int)y, (int)z);
-      ld = node_lin(dst, (int)x, (int)y, (int)z);
-    }
-    bool sf, df;
-    const long long so = channel_offset(src, ls, ch, K, sf);
-    const long long doff = channel_offset(dst, ld, ch, K, df);
-    (df ? dst_first : dst_second)[doff] = (sf ? src.dens : src.feat)[so];
-  }
-}
-
-// The common case of the re-layout -- reference tensors -> split tensors, both in linear node order, whole quads per node (SH degree
-// 0 or 2) -- one thread per destination float4: quad 0 of a node = (density, degree-0 r, g, b), quad q >= 1 = rest[4 (q - 1) ..].
-// The four source floats are 4-byte gathers inside the node's 108-byte feature record (cache hits); the store is a coalesced 16 B.
-template <int K>
-__global__ void reference_to_split_kernel(const float* __restrict__ dens, const float* __restrict__ feat, long long dstride, long long fstride,
-                                          float4* __restrict__ base, float4* __restrict__ rest, unsigned int nodes) {
-  constexpr int QN = (3 * K + 1) / 4;  // quads per node
-  constexpr int KR = K > 1 ? K - 1 : 1;
-  const unsigned int total = nodes * QN;
-  for (unsigned int it = blockIdx.x * blockDim.x + threadIdx.x; it < total; it += gridDim.x * blockDim.x) {
-    const unsigned int node = it / QN, q = it - node * QN;
-    const float* f = feat + (long long)node * fstride;
-    if (q == 0) {
-      base[node] = make_float4(dens[(long long)node * dstride], f[0], f[K], f[2 * K]);
-    } else {
-      float v[4];
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const unsigned int r = 4 * (q - 1) + x;
-        const unsigned int colour = r / KR, k = r - colour * KR + 1;
-        v[x] = f[colour * K + k];
-      }
-      rest[(long long)node * (QN - 1) + (q - 1)] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-  }
-}
-
-// ... and back: split tensors -> reference tensors, one thread per SOURCE float4 (coalesced 16-byte load, four 4-byte stores inside the
-// node's feature record).  Used when the split shadow is the copy the optimizer updated (deferred gradients, optim.FlatGrid).
-template <int K>
-__global__ void split_to_reference_kernel(const float4* __restrict__ base, const float4* __restrict__ rest, float* __restrict__ dens,
-                                          float* __restrict__ feat, long long dstride, long long fstride, unsigned int nodes) {
-  constexpr int QN = (3 * K + 1) / 4;
-  constexpr int KR = K > 1 ? K - 1 : 1;
-  const unsigned int total = nodes * QN;
-  for (unsigned int it = blockIdx.x * blockDim.x + threadIdx.x; it < total; it += gridDim.x * blockDim.x) {
-    const unsigned int node = it / QN, q = it - node * QN;
-    float* f = feat + (long long)node * fstride;
-    if (q == 0) {
-      const float4 v = base[node];
-      dens[(long long)node * dstride] = v.x;
-      f[0] = v.y;
-      f[K] = v.z;
-      f[2 * K] = v.w;
-    } else {
-      const float4 v4 = rest[(long long)node * (QN - 1) + (q - 1)];
-      const float v[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int x = 0; x < 4; ++x) {
-        const unsigned int r = 4 * (q - 1) + x;
-        const unsigned int colour = r / KR, k = r - colour * KR + 1;
-        f[colour * K + k] = v[x];
-      }
-    }
-  }
-}
-
-// The same re-layout with coalesced 16-byte STORES for contiguous reference tensors (features [nodes * F] and densities [nodes] written
-// as float4s, each gathering its four source floats -- cache hits inside the nodes' base / rest records): 0.164 -> ms of the per-element
-// store version on the 128^3 / SH-2 grid.
-template <int K>
-__global__ void split_to_reference_quads_kernel(const float* __restrict__ base, const float* __restrict__ rest, float4* __restrict__ dens4,
-                                                float4* __restrict__ feat4, unsigned int nodes) {
-  constexpr unsigned int F = 3 * K, R = F - 3;
-  constexpr unsigned int KR = K > 1 ? K - 1 : 1;
-  const unsigned int fq = nodes * F / 4, dq = nodes / 4;  // (host-checked: nodes % 4 == 0)
-  for (unsigned int it = blockIdx.x * blockDim.x + threadIdx.x; it < fq + dq; it += gridDim.x * blockDim.x) {
-    float v[4];
-    if (it < fq) {
-#pragma unroll
-      for (unsigned int x = 0; x < 4; ++x) {
-        const unsigned int f = 4 * it + x, node = f / F, c = f - node * F;
-        const unsigned int colour = c / K, k = c - colour * K;
-        v[x] = (k == 0) ? base[node * 4 + 1 + colour] : rest[node * R + colour * KR + (k - 1)];
-      }
-      feat4[it] = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-      const unsigned int n0 = 4 * (it - fq);
-      dens4[it - fq] = make_float4(base[n0 * 4], base[n0 * 4 + 4], base[n0 * 4 + 8], base[n0 * 4 + 12]);
-    }
-  }
-}
-
-// =============================================================================================
-// standalone point query: VoxelGrid.forward (thre3d_reprs/voxels.py:276-331) and its adjoint.
-// One thread per (point, output channel); channel c < F is feature c in the reference order (colour*K + k),
-// channel F is the activated density.  Any point is allowed (zeros padding outside the grid, no AABB mask --
-// the mask belongs to process_points).  Not a hot path: the renderer uses the fused kernels above.
-// =============================================================================================
-struct QueryCorner {
-  long long lin;
-  float w;
-  bool ok;
-};
-
-__device__ __forceinline__ void query_cell(const float p[3], const GridArgs& g, int i0[3], float w0[3], float w1[3]) {
-  const int dims[3] = {g.X, g.Y, g.Z};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float q = p[a] * g.nscale[a] + g.nbias[a];
-    const float idx = ((q + 1.0f) * (float)dims[a] - 1.0f) / 2.0f;
-    const float fl = floorf(idx);
-    w1[a] = idx - fl;
-    w0[a] = (fl + 1.0f) - idx;
-    // far-away points: every corner is outside anyway; clamp so that the integer conversion is defined
-    i0[a] = (int)fminf(fmaxf(fl, -2.0f), (float)dims[a]);
-  }
-}
-
-__device__ __forceinline__ QueryCorner query_corner(int k, const int i0[3], const float w0[3], const float w1[3],
-                                                    const GridArgs& g) {
-  const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-  const int ix = i0[0] + dx, iy = i0[1] + dy, iz = i0[2] + dz;
-  QueryCorner c;
-  c.ok = ix >= 0 && ix < g.X && iy >= 0 && iy < g.Y && iz >= 0 && iz < g.Z;
-  c.lin = node_lin(g, min(max(ix, 0), g.X - 1), min(max(iy, 0), g.Y - 1), min(max(iz, 0), g.Z - 1));
-  c.w = ((dx ? w1[0] : w0[0]) * (dy ? w1[1] : w0[1])) * (dz ? w1[2] : w0[2]);
-  return c;
-}
-
-// element offset of output channel c of voxel `lin` inside the tensor that holds it; *in_first = it is the
-// densities/base tensor rather than the features/rest tensor
-__device__ __forceinline__ long long query_offset(int c, long long lin, const GridArgs& g, bool* in_first) {
-  const int F = g.F, K = F / 3;
-  if (c == F) {
-    *in_first = true;
-    return lin * g.dstride;
-  }
-  if (g.layout == RF_LAYOUT_SPLIT) {
-    const int ch = c / K, k = c % K;
-    if (k == 0) {
-      *in_first = true;
-      return lin * g.dstride + 1 + ch;
-    }
-    *in_first = false;
-    return lin * g.fstride + ch * (K - 1) + (k - 1);
-  }
-  *in_first = false;
-  return lin * g.fstride + c;
-}
-
-__device__ __forceinline__ float density_post(float pre, int mode) {
-  if (mode == RF_DENSITY_RELU) return fmaxf(pre, 0.0f);
-  if (mode == RF_DENSITY_SOFTPLUS) return (pre > 20.0f) ? pre : log1pf(expf(pre));
-  return pre;
-}
-
-__global__ void grid_query_kernel(GridArgs g, const float* __restrict__ points, long long n, float* __restrict__ out) {
-  const int C = g.F + 1;
-  const long long total = n * C;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long long)gridDim.x * blockDim.x) {
-    const long long pt = idx / C;
-    const int c = (int)(idx % C);
-    const float p[3] = {points[pt * 3], points[pt * 3 + 1], points[pt * 3 + 2]};
-    int i0[3];
-    float w0[3], w1[3];
-    query_cell(p, g, i0, w0, w1);
-    const bool dens = (c == g.F);
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const QueryCorner qc = query_corner(k, i0, w0, w1, g);
-      if (qc.ok) {
-        bool first;
-        const long long off = query_offset(c, qc.lin, g, &first);
-        float v = first ? g.dens[off] : g.feat[off];
-        if (dens) {
-          v = v * g.rho;
-          if (g.mode == RF_DENSITY_ABS) v = fabsf(v);
-        }
-        acc = acc + v * qc.w;
-      }
-    }
-    out[idx] = dens ? density_post(acc, g.mode) : acc;
-  }
-}
-
-__global__ void grid_query_backward_kernel(GridArgs g, const float* __restrict__ points, long long n,
-                                           const float* __restrict__ gout, float* gfirst, float* gsecond) {
-  const int C = g.F + 1;
-  const long long total = n * C;
-  for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-       idx += (long long)gridDim.x * blockDim.x) {
-    const long long pt = idx / C;
-    const int c = (int)(idx % C);
-    float go = gout[idx];
-    if (go == 0.0f) continue;
-    const float p[3] = {points[pt * 3], points[pt * 3 + 1], points[pt * 3 + 2]};
-    int i0[3];
-    float w0[3], w1[3];
-    query_cell(p, g, i0, w0, w1);
-    const bool dens = (c == g.F);
-    if (dens && (g.mode == RF_DENSITY_RELU || g.mode == RF_DENSITY_SOFTPLUS)) {
-      float pre = 0.0f;  // the activation derivative needs the interpolated pre-activation
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const QueryCorner qc = query_corner(k, i0, w0, w1, g);
-        if (qc.ok) pre = pre + (g.dens[qc.lin * g.dstride] * g.rho) * qc.w;
-      }
-      if (g.mode == RF_DENSITY_RELU)
-        go = (pre > 0.0f) ? go : 0.0f;
-      else
-        go = go * ((pre > 20.0f) ? 1.0f : 1.0f / (1.0f + expf(-pre)));
-      if (go == 0.0f) continue;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const QueryCorner qc = query_corner(k, i0, w0, w1, g);
-      if (!qc.ok) continue;
-      bool first;
-      const long long off = query_offset(c, qc.lin, g, &first);
-      float gv = qc.w * go;
-      if (dens) {
-        gv = gv * g.rho;
-        if (g.mode == RF_DENSITY_ABS) {
-          const float dv = g.dens[off] * g.rho;
-          gv = (dv > 0.f) ? gv : ((dv < 0.f) ? -gv : 0.0f);
-        }
-      }
-      if (gv != 0.0f) unsafeAtomicAdd((first ? gfirst : gsecond) + off, gv);
-    }
-  }
-}
-
-// =============================================================================================
-// ray and point adjoints: dL/d(origins, directions) of a render, dL/d(points) of a grid query
-//
-// Shared piece: the gradient of a trilinear interpolation with respect to the CONTINUOUS index.  With the corner weights
-// w_k = wx_dx wy_dy wz_dz (w1_a = idx_a - floor, w0_a = floor + 1 - idx_a, so w1_a' = +1, w0_a' = -1) and q_k the per-corner value
-// the upstream gradient sees, d/d idx_a sum_k w_k q_k = sum_k (d w_k / d idx_a) q_k.  The same floor cell, zero padding and corner
-// skipping as the forward (corners outside the grid contribute nothing).  J = diag(nscale_a size_a / 2) maps index to world.
-// =============================================================================================
-// d w_k / d idx of corner k = dx + 2 dy + 4 dz (a corner inside the grid; the caller skips the others)
-__device__ __forceinline__ void corner_index_grad(int k, const float w0[3], const float w1[3], float dw[3]) {
-  const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-  const float wx = dx ? w1[0] : w0[0], wy = dy ? w1[1] : w0[1], wz = dz ? w1[2] : w0[2];
-  const float sx = dx ? 1.0f : -1.0f, sy = dy ? 1.0f : -1.0f, sz = dz ? 1.0f : -1.0f;
-  dw[0] = (sx * wy) * wz;
-  dw[1] = (wx * sy) * wz;
-  dw[2] = (wx * wy) * sz;
-}
-
-__device__ __forceinline__ void index_to_world(const GridArgs& g, float gi[3]) {
-  const int dims[3] = {g.X, g.Y, g.Z};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) gi[a] = gi[a] * (g.nscale[a] * (float)dims[a] * 0.5f);
-}
-
-// sum_k G_k dY_k/dv of the signed basis of sh_basis<K> (v = (x, y, z) unit)
-template <int K>
-__device__ __forceinline__ void sh_basis_vjp(float x, float y, float z, const float G[16], float gv[3]) {
-  gv[0] = gv[1] = gv[2] = 0.0f;
-  if (K > 1) {
-    gv[1] += -kC1 * G[1];
-    gv[2] += kC1 * G[2];
-    gv[0] += -kC1 * G[3];
-  }
-  if (K > 4) {
-    gv[0] += kC2_0 * y * G[4];
-    gv[1] += kC2_0 * x * G[4];
-    gv[1] += kC2_1 * z * G[5];
-    gv[2] += kC2_1 * y * G[5];
-    gv[0] += -2.0f * kC2_2 * x * G[6];
-    gv[1] += -2.0f * kC2_2 * y * G[6];
-    gv[2] += 4.0f * kC2_2 * z * G[6];
-    gv[0] += kC2_3 * z * G[7];
-    gv[2] += kC2_3 * x * G[7];
-    gv[0] += 2.0f * kC2_4 * x * G[8];
-    gv[1] += -2.0f * kC2_4 * y * G[8];
-  }
-  if (K > 9) {
-    const float xx = x * x, yy = y * y, zz = z * z;
-    gv[0] += 6.0f * kC3_0 * x * y * G[9];
-    gv[1] += kC3_0 * (3.0f * xx - 3.0f * yy) * G[9];
-    gv[0] += kC3_1 * y * z * G[10];
-    gv[1] += kC3_1 * x * z * G[10];
-    gv[2] += kC3_1 * x * y * G[10];
-    gv[0] += -2.0f * kC3_2 * x * y * G[11];
-    gv[1] += kC3_2 * (4.0f * zz - xx - 3.0f * yy) * G[11];
-    gv[2] += 8.0f * kC3_2 * y * z * G[11];
-    gv[0] += -6.0f * kC3_3 * x * z * G[12];
-    gv[1] += -6.0f * kC3_3 * y * z * G[12];
-    gv[2] += kC3_3 * (6.0f * zz - 3.0f * xx - 3.0f * yy) * G[12];
-    gv[0] += kC3_4 * (4.0f * zz - 3.0f * xx - yy) * G[13];
-    gv[1] += -2.0f * kC3_4 * x * y * G[13];
-    gv[2] += 8.0f * kC3_4 * x * z * G[13];
-    gv[0] += 2.0f * kC3_5 * x * z * G[14];
-    gv[1] += -2.0f * kC3_5 * y * z * G[14];
-    gv[2] += kC3_5 * (xx - yy) * G[14];
-    gv[0] += kC3_6 * (3.0f * xx - 3.0f * yy) * G[15];
-    gv[1] += -6.0f * kC3_6 * x * y * G[15];
-  }
-}
-
-// feature k of colour ch at node `lin` (KG = coefficients per colour stored in the grid): reference [F] = colour * KG + k;
-// split / bricked: k == 0 in the base record (sigma, r, g, b), k > 0 in the rest record at colour * (KG - 1) + k - 1
-__device__ __forceinline__ float node_feature(const GridArgs& g, long long lin, int ch, int k, int KG) {
-  if (g.layout == RF_LAYOUT_SPLIT) {
-    if (k == 0) return g.dens[lin * g.dstride + 1 + ch];
-    return g.feat[lin * g.fstride + ch * (KG - 1) + (k - 1)];
-  }
-  return g.feat[lin * g.fstride + ch * KG + k];
-}
-
-// The slab test of ray_box with the derivative of the bound each running max / min kept: bound = (plane - o_a) / (d_a + 1e-10) of
-// axis `axis`, so d bound / d o_a = -1 / den, d bound / d d_a = -bound / den.  `ok` = the bound reaches the sampler (a hit, and not
-// clipped to 0 -- torch.clamp passes the gradient at >= 0).  Selections follow ray_box (and the reference's torch.where order).
-struct BoundGrad {
-  int axis;
-  float dd_o, dd_d;  // d bound / d o_axis, d bound / d d_axis
-  bool ok;
-};
-__device__ __forceinline__ void ray_box_grad(const float o[3], const float d[3], const float bmin[3], const float bmax[3], BoundGrad& glo,
-                                             BoundGrad& ghi) {
-  float lo_run = 0.f, hi_run = 0.f, lo_den = 1.f, hi_den = 1.f;
-  int lo_ax = 0, hi_ax = 0;
-  bool hit = true;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float den = d[a] + kZeroPlus;
-    const float ta = (bmin[a] - o[a]) / den;
-    const float tb = (bmax[a] - o[a]) / den;
-    const bool swap = ta > tb;
-    const float lo = swap ? tb : ta;
-    const float hi = swap ? ta : tb;
-    if (a == 0) {
-      lo_run = lo;
-      hi_run = hi;
-      lo_den = hi_den = den;
-    } else {
-      hit = hit && !((lo_run > hi) || (lo > hi_run));
-      if (lo > lo_run) {
-        lo_run = lo;
-        lo_ax = a;
-        lo_den = den;
-      }
-      if (hi < hi_run) {
-        hi_run = hi;
-        hi_ax = a;
-        hi_den = den;
-      }
-    }
-  }
-  glo.axis = lo_ax;
-  glo.dd_o = -1.0f / lo_den;
-  glo.dd_d = -lo_run / lo_den;
-  glo.ok = hit && lo_run >= 0.0f;
-  ghi.axis = hi_ax;
-  ghi.dd_o = -1.0f / hi_den;
-  ghi.dd_d = -hi_run / hi_den;
-  ghi.ok = hit && hi_run >= 0.0f;
-}
-
-// =============================================================================================
-// dL/d(origins), dL/d(directions) of rf_render_forward (the reference gets them from autograd through _ray_aabb_intersection,
-// grid_sample's grid gradient, the SH basis and the interval lengths).  Notation of render_backward_kernel: e_i, w_i, T_i,
-// E_i = exp(-sigma_i delta_i); x_i = o + z_i d, delta_i = (z_{i+1} - z_i) |d| (1e10 |d| for the last sample), v = d / |d|.
-//   g_delta_i = sigma_i (T_i E_i e_i - sum_{j>i} w_j e_j)            (the bracket of g_sigma_i, times sigma instead of delta)
-//   g_x_i     = J^T [ g_pre_i grad interp(pre(rho D)) + sum_ch g_raw_i[ch] grad interp(sum_k Y_k(v) f_{ch,k}) ]
-//   g_v       = sum_i sum_ch g_raw_i[ch] sum_k interp(f_{ch,k})(x_i) dY_k/dv
-//   g_|d|     = sum_{i<S-1} g_delta_i (z_{i+1} - z_i) + 1e10 g_delta_{S-1}
-//   g_o = sum_i g_x_i;   g_d = sum_i z_i g_x_i + g_|d| v + (I - v v^T) g_v / |d|
-// and, under RF_FLAG_AABB_SAMPLING only, the z_i = lo (1 - tau_i) + hi tau_i chain through the per-ray bounds of the slab test:
-//   g_z_i = g_x_i . d + gD w_i - |d| g_delta_i + |d| g_delta_{i-1};  g_lo = sum g_z_i (1 - tau_i), g_hi = sum g_z_i tau_i.
-// One wavefront per ray, lanes = samples, the chunks walked far to near with the running suffix sum of render_backward_kernel and
-// make_sample's arithmetic (bit-identical cells and weights); each cached sample's lane gathers its 8 corners itself.  Every
-// per-ray sum is a wave reduction: no atomics, bitwise deterministic.
-// Uncached samples (outside the box, behind T = 0, sigma = 0 under ReLU) contribute nothing to g_x, g_v or g_delta -- but a
-// cached sample i still couples to z_{i+1} through delta_i: that +|d| g_delta_i term is attributed HERE, at sample i, with the
-// recomputed tau_{i+1}, since sample i+1 (empty space behind a surface, say) may have no cache entry and no lane work at all.
-// =============================================================================================
-template <int K, bool DIFFUSE>
-__global__ __launch_bounds__(kBlock) void render_backward_rays_kernel(GridArgs g, RayArgs r, OutArgs fwd, GradArgs gr, uint32_t flags,
-                                                                      float* __restrict__ g_orig, float* __restrict__ g_dir) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
-  if (ray >= r.n) return;
-
-  const RayState st = load_ray(r, g, ray, flags);
-  const bool aabb = flags & RF_FLAG_AABB_SAMPLING;
-  const float white = (flags & RF_FLAG_WHITE_BKGD) ? 1.0f : 0.0f;
-  float gC[3] = {0.f, 0.f, 0.f};
-  if (gr.gcolour) {
-    gC[0] = gr.gcolour[ray * 3 + 0];
-    gC[1] = gr.gcolour[ray * 3 + 1];
-    gC[2] = gr.gcolour[ray * 3 + 2];
-  }
-  const float gD = gr.gdepth ? gr.gdepth[ray] : 0.0f;
-  const float gA = gr.gacc ? gr.gacc[ray] : 0.0f;
-  const float v[3] = {st.d[0] / st.dnorm, st.d[1] / st.dnorm, st.d[2] / st.dnorm};
-  float Y[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) Y[k] = 0.0f;
-  if (DIFFUSE || K == 1)
-    Y[0] = kC0;
-  else
-    sh_basis<K>(v[0], v[1], v[2], Y);
-  const int KG = g.F / 3;
-  RayState st01 = st;  // the same sampler on [0, 1]: tau_i (z_uniform(0, 1, t) == t exactly)
-  st01.near = 0.0f;
-  st01.far = 1.0f;
-
-  // per-lane partial sums
-  float go[3] = {0.f, 0.f, 0.f}, gdz[3] = {0.f, 0.f, 0.f}, gdn = 0.0f, glo = 0.0f, ghi = 0.0f;
-  float Gk[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) Gk[k] = 0.0f;
-
-  const int processed = fwd.stop[ray];
-  const int nchunks = (processed + kWave - 1) / kWave;
-  const int mask_words = (r.S + kWave - 1) / kWave;
-  float suffix = 0.0f;
-  unsigned long long lane_masks = 0ull;
-  int masks_group = -1;
-  for (int chunk = nchunks - 1; chunk >= 0; --chunk) {
-    const int s = chunk * kWave + lane;
-    if ((chunk >> 6) != masks_group) {
-      masks_group = chunk >> 6;
-      const int c = masks_group * kWave + lane;
-      lane_masks = fwd.cmask[ray * (long long)mask_words + min(c, mask_words - 1)];
-    }
-    const unsigned long long cm = chunk_mask_of(lane_masks, chunk);
-    if (cm == 0ull) continue;
-    const float z = z_of(st, r, ray, s), zn = z_of(st, r, ray, s + 1);
-    const Sample sm = sample_at(st, r, g, s, z, zn);  // == make_sample
-    const bool have = (cm >> lane) & 1ull;
-    float raw[3] = {0.f, 0.f, 0.f};
-    float sigma = 0.f, T = 0.f;
-    {
-      const long long idx = cached_slot(ray, r.S, chunk, cm, lane);
-      const float4 cv = reinterpret_cast<const float4*>(fwd.cache)[idx];
-      const float Tl = fwd.tcache[idx];
-      if (have) {
-        raw[0] = cv.x;
-        raw[1] = cv.y;
-        raw[2] = cv.z;
-        sigma = cv.w;
-        T = Tl;
-      }
-    }
-    float E;
-    const float alpha = occupancy_alpha(sigma * sm.delta, E);
-    const float w = alpha * T;
-    const float Tn = T * E;
-    float c[3], e = gD * sm.z + gA;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      c[ch] = sigmoidf_(raw[ch]);
-      e += gC[ch] * (c[ch] - white);
-    }
-    const float we = have ? w * e : 0.0f;
-    const float incl = wave_incl_rscan_add(we, lane);
-    const float after = (incl - we) + suffix;
-    suffix += __shfl(incl, 0, kWave);
-    if (!(have && sm.inside)) continue;
-
-    const float bracket = Tn * e - after;
-    const float g_sigma = sm.delta * bracket;
-    const float g_delta = sigma * bracket;
-    float g_pre;
-    if (g.mode == RF_DENSITY_RELU)
-      g_pre = (sigma > 0.0f) ? g_sigma : 0.0f;
-    else if (g.mode == RF_DENSITY_SOFTPLUS)
-      g_pre = g_sigma * softplus_slope(sigma);
-    else
-      g_pre = g_sigma;
-    float g_raw[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) g_raw[ch] = (w * gC[ch]) * (c[ch] * (1.0f - c[ch]));
-
-    // the 8 corners: q_k = g_pre pre(rho D_k) + sum_ch g_raw[ch] sum_k' Y_k' f_{ch,k'}
-    const Cell& cl = sm.cell;
-    const bool okx[2] = {cl.i0[0] >= 0, cl.i0[0] + 1 < g.X};
-    const bool oky[2] = {cl.i0[1] >= 0, cl.i0[1] + 1 < g.Y};
-    const bool okz[2] = {cl.i0[2] >= 0, cl.i0[2] + 1 < g.Z};
-    float gx[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-      const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-      if (!(okx[dx] && oky[dy] && okz[dz])) continue;
-      const long long lin = node_lin(g, cl.i0[0] + dx, cl.i0[1] + dy, cl.i0[2] + dz);
-      float dv = g.dens[lin * g.dstride] * g.rho;
-      if (g.mode == RF_DENSITY_ABS) dv = fabsf(dv);
-      const float wk = ((dx ? cl.w1[0] : cl.w0[0]) * (dy ? cl.w1[1] : cl.w0[1])) * (dz ? cl.w1[2] : cl.w0[2]);
-      float qk = g_pre * dv;
-#pragma unroll
-      for (int kk = 0; kk < (DIFFUSE ? 1 : K); ++kk) {
-        const float f0 = node_feature(g, lin, 0, kk, KG), f1 = node_feature(g, lin, 1, kk, KG), f2 = node_feature(g, lin, 2, kk, KG);
-        const float mix = (g_raw[0] * f0 + g_raw[1] * f1) + g_raw[2] * f2;
-        qk += Y[kk] * mix;
-        if (!DIFFUSE && K > 1) Gk[kk] += wk * mix;
-      }
-      float dw[3];
-      corner_index_grad(k, cl.w0, cl.w1, dw);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) gx[a] += dw[a] * qk;
-    }
-    index_to_world(g, gx);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      go[a] += gx[a];
-      gdz[a] += sm.z * gx[a];
-    }
-    const bool last = s == r.S - 1;
-    gdn += last ? kInfinity * g_delta : g_delta * (zn - sm.z);
-    if (aabb) {
-      const float own = ((gx[0] * st.d[0] + gx[1] * st.d[1]) + gx[2] * st.d[2]) + gD * w - (last ? 0.0f : st.dnorm * g_delta);
-      const float tau = z_of(st01, r, ray, s);
-      glo += own * (1.0f - tau);
-      ghi += own * tau;
-      if (!last) {  // +|d| g_delta_i on z_{i+1}, whether or not sample i+1 is cached
-        const float nxt = st.dnorm * g_delta, tau1 = z_of(st01, r, ray, s + 1);
-        glo += nxt * (1.0f - tau1);
-        ghi += nxt * tau1;
-      }
-    }
-  }
-
-  // per-ray sums (every lane ends with the totals)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    go[a] = wave_sum(go[a]);
-    gdz[a] = wave_sum(gdz[a]);
-  }
-  gdn = wave_sum(gdn);
-  glo = wave_sum(glo);
-  ghi = wave_sum(ghi);
-  float gv[3] = {0.f, 0.f, 0.f};
-  if (!DIFFUSE && K > 1) {
-#pragma unroll
-    for (int k = 1; k < K; ++k) Gk[k] = wave_sum(Gk[k]);
-    sh_basis_vjp<K>(v[0], v[1], v[2], Gk, gv);
-  }
-  if (lane != 0) return;
-  const float vg = (v[0] * gv[0] + v[1] * gv[1]) + v[2] * gv[2];
-  float gd[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) gd[a] = gdz[a] + gdn * v[a] + (gv[a] - vg * v[a]) / st.dnorm;
-  if (aabb) {
-    BoundGrad blo, bhi;
-    ray_box_grad(st.o, st.d, g.amin, g.amax, blo, bhi);
-    if (blo.ok) {
-      go[blo.axis] += glo * blo.dd_o;
-      gd[blo.axis] += glo * blo.dd_d;
-    }
-    if (bhi.ok) {
-      go[bhi.axis] += ghi * bhi.dd_o;
-      gd[bhi.axis] += ghi * bhi.dd_d;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (g_orig) g_orig[ray * 3 + a] = go[a];
-    if (g_dir) g_dir[ray * 3 + a] = gd[a];
-  }
-}
-
-// dL/d(points) of grid_query_kernel: one thread per point, the corner values of every output channel folded with its upstream
-// gradient (the density channel's after the activation slope: ReLU [interp > 0], softplus sigmoid below the threshold 20)
-__global__ void grid_query_backward_points_kernel(GridArgs g, const float* __restrict__ points, long long n, const float* __restrict__ gout,
-                                                  float* __restrict__ gpoints) {
-  const int C = g.F + 1;
-  for (long long pt = (long long)blockIdx.x * blockDim.x + threadIdx.x; pt < n; pt += (long long)gridDim.x * blockDim.x) {
-    const float p[3] = {points[pt * 3], points[pt * 3 + 1], points[pt * 3 + 2]};
-    int i0[3];
-    float w0[3], w1[3];
-    query_cell(p, g, i0, w0, w1);
-    float gden = gout[pt * C + g.F];
-    if (g.mode == RF_DENSITY_RELU || g.mode == RF_DENSITY_SOFTPLUS) {
-      float pre = 0.0f;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const QueryCorner qc = query_corner(k, i0, w0, w1, g);
-        if (qc.ok) pre = pre + (g.dens[qc.lin * g.dstride] * g.rho) * qc.w;
-      }
-      if (g.mode == RF_DENSITY_RELU)
-        gden = (pre > 0.0f) ? gden : 0.0f;
-      else
-        gden = gden * ((pre > 20.0f) ? 1.0f : 1.0f / (1.0f + expf(-pre)));
-    }
-    float gi[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int k = 0; k < 8; ++k) {
-      const QueryCorner qc = query_corner(k, i0, w0, w1, g);
-      if (!qc.ok) continue;
-      float dv = g.dens[qc.lin * g.dstride] * g.rho;
-      if (g.mode == RF_DENSITY_ABS) dv = fabsf(dv);
-      float acc = gden * dv;
-      for (int c = 0; c < g.F; ++c) {
-        bool first;
-        const long long off = query_offset(c, qc.lin, g, &first);
-        acc += gout[pt * C + c] * (first ? g.dens[off] : g.feat[off]);
-      }
-      float dw[3];
-      corner_index_grad(k, w0, w1, dw);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) gi[a] += dw[a] * acc;
-    }
-    index_to_world(g, gi);
-#pragma unroll
-    for (int a = 0; a < 3; ++a) gpoints[pt * 3 + a] = gi[a];
-  }
-}
-
-// =============================================================================================
 // ray generation (rendering/volumetric/utils/misc.py:12-50)
 // =============================================================================================
 struct Pose {
   float r[9];
   float t[3];
 };
-
 
 __global__ void cast_rays_kernel(int H, int W, float focal, Pose pose, float* origins, float* dirs) {
   const long long n = (long long)H * W;
@@ -4282,40 +2953,6 @@ __global__ void ray_aabb_bounds_kernel(const float* origins, const float* dirs, 
     bounds[q * 2] = t0;
     bounds[q * 2 + 1] = t1;
     if (hit) hit[q] = h ? 1.0f : 0.0f;
-  }
-}
-
-// =============================================================================================
-// occupancy mask (exact empty-space skipping for the ReLU field)
-// =============================================================================================
-__global__ void build_occupancy_kernel(GridArgs g, float threshold, uint32_t* occ, long long nwords) {
-  // one lane per cell, 64 consecutive cells (z fastest) per wave -> two mask words per __ballot; the 8 nodes of
-  // neighbouring cells overlap, so the loads hit L1
-  const long long ncell = (long long)(g.X + 1) * (g.Y + 1) * (g.Z + 1);
-  const long long nwave_items = (ncell + 63) / 64;
-  const int lane = threadIdx.x & 63;
-  const long long wave0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const long long wave_stride = ((long long)gridDim.x * blockDim.x) >> 6;
-  for (long long item = wave0; item < nwave_items; item += wave_stride) {
-    const long long cell = item * 64 + lane;
-    bool occ_cell = false;
-    if (cell < ncell) {
-      occ_cell = (g.mode != RF_DENSITY_RELU);
-      if (!occ_cell) {
-        const int cz = (int)(cell % (g.Z + 1));
-        const long long t = cell / (g.Z + 1);
-        const int cy = (int)(t % (g.Y + 1)), cx = (int)(t / (g.Y + 1));
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int x = cx - 1 + (k & 1), y = cy - 1 + ((k >> 1) & 1), z = cz - 1 + (k >> 2);
-          if (x >= 0 && x < g.X && y >= 0 && y < g.Y && z >= 0 && z < g.Z)
-            occ_cell = occ_cell || (g.dens[(long long)node_lin(g, x, y, z) * g.dstride] * g.rho > threshold);
-        }
-      }
-    }
-    const unsigned long long bits = __ballot(occ_cell);
-    if (lane == 0 && item * 2 < nwords) occ[item * 2] = (uint32_t)bits;
-    if (lane == 32 && item * 2 + 1 < nwords) occ[item * 2 + 1] = (uint32_t)(bits >> 32);
   }
 }
 
@@ -4474,866 +3111,7 @@ __global__ __launch_bounds__(1024) void loss_and_offsets_kernel(L1Sets sets, con
   }
 }
 
-// =============================================================================================
-// rf_tv_grad: total variation of the raw grid parameters.  For node n and channel c, with
-// d_a(n) = theta[n + e_a] - theta[n] (0 where n + e_a lies outside the grid) and r(n) = sqrt(eps + sum_a d_a(n)^2):
-//   g(n) = w * [ -(d_x(n) + d_y(n) + d_z(n)) / r(n) + sum_a d_a(n - e_a) / r(n - e_a) ]      (terms outside the grid dropped)
-// GATHER form: one thread owns V consecutive channels of one (y, z) column of an x-slab of kTvSlab nodes, reads the parameters
-// only, and adds g to its own gradient elements -- no atomics on the gradient, bitwise reproducible.  Lanes run over the
-// (z, channel) row, so every neighbour load of a wave is a contiguous row segment (split storage, SH degree 0 / 2: one float4 of a
-// node per lane).  Walking x in registers, the centre, its -y and its -z neighbour are the +x loads of the plane before and the
-// x term d_x(n - e_x) / r(n - e_x) is the plane before's own d_x / r: 7 parameter loads per element instead of 13, the rest
-// served by L1 / L2 (the four waves of a workgroup are four neighbouring y rows).  Padding nodes of bricked storage are never
-// addressed: every neighbour is tested against the grid's dims first.
-// =============================================================================================
-constexpr int kTvSlab = 8;   // x planes per workgroup
-constexpr int kTvRows = 4;   // y rows per workgroup (one wave each)
-
-template <int V>
-struct TvVec {
-  float v[V];
-};
-template <int V>
-__device__ __forceinline__ TvVec<V> tv_load(const float* p) {
-  TvVec<V> r;
-  if constexpr (V == 4) {
-    const float4 q = *reinterpret_cast<const float4*>(p);
-    r.v[0] = q.x, r.v[1] = q.y, r.v[2] = q.z, r.v[3] = q.w;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-template <int V>
-__device__ __forceinline__ void tv_store(float* p, const TvVec<V>& r) {
-  if constexpr (V == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-  } else {
-    *p = r.v[0];
-  }
-}
-// 1 / r = 1 / sqrt(eps + dx^2 + dy^2 + dz^2): three fused multiply-adds, a correctly rounded square root and division
-__device__ __forceinline__ float tv_inv_norm(float dx, float dy, float dz, float eps) {
-  return 1.0f / sqrtf(fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps))));
-}
-
-template <int K, int V, bool SUMS>
-__global__ __launch_bounds__(kWave * kTvRows) void tv_grad_kernel(GridArgs g, float wd, float wf, float eps, float* __restrict__ gfirst,
-                                                                  float* __restrict__ gsecond, float* __restrict__ sums) {
-  constexpr int C = 3 * K + 1, Q = C / V;  // channels per node in accumulator order (channel_offset), lanes per node
-  const unsigned it = blockIdx.x * kWave + threadIdx.x;
-  const int z = (int)(it / Q), ch = (int)(it - (unsigned)z * Q) * V;
-  const int y = blockIdx.y * kTvRows + threadIdx.y;
-  const int x0 = blockIdx.z * kTvSlab, x1 = min(x0 + kTvSlab, g.X);
-  float sum_d = 0.0f, sum_f = 0.0f;
-  float w[V];
-  bool write = false;
-#pragma unroll
-  for (int c = 0; c < V; ++c) {
-    w[c] = (ch + c == 0) ? wd : wf;
-    write = write || w[c] != 0.0f;
-  }
-  if (y < g.Y && z < g.Z && (write || SUMS)) {
-    bool first;
-    const long long coff = channel_offset(g, 0u, ch, K, first);  // the channel's place inside a node's record
-    const float* src = (first ? g.dens : g.feat) + coff;
-    float* dst = (first ? gfirst : gsecond) + coff;
-    const long long stride = first ? g.dstride : g.fstride;
-    auto off = [&](int xi, int yi, int zi) { return (long long)node_lin(g, xi, yi, zi) * stride; };
-    auto at = [&](int xi, int yi, int zi) { return tv_load<V>(src + off(xi, yi, zi)); };
-    const bool ly = y > 0, lz = z > 0, hy = y + 1 < g.Y, hz = z + 1 < g.Z;
-    TvVec<V> t = at(x0, y, z), my = t, mz = t, tx;
-    if (ly) my = at(x0, y - 1, z);
-    if (lz) mz = at(x0, y, z - 1);
-    if (x0 > 0) {  // the x term of the slab's first plane, computed the way the loop computes it for the plane before
-      const TvVec<V> m = at(x0 - 1, y, z), py = hy ? at(x0 - 1, y + 1, z) : m, pz = hz ? at(x0 - 1, y, z + 1) : m;
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float dx = t.v[c] - m.v[c];
-        tx.v[c] = dx * tv_inv_norm(dx, py.v[c] - m.v[c], pz.v[c] - m.v[c], eps);
-      }
-    }
-    for (int x = x0; x < x1; ++x) {
-      const bool hx = x + 1 < g.X;
-      // a missing upper neighbour is replaced by the node itself: its difference is then exactly 0
-      const TvVec<V> fx = hx ? at(x + 1, y, z) : t, fy = hy ? at(x, y + 1, z) : t, fz = hz ? at(x, y, z + 1) : t;
-      TvVec<V> myx = my, myz = my, mzx = mz, mzy = mz;
-      if (ly) {
-        if (hx) myx = at(x + 1, y - 1, z);
-        if (hz) myz = at(x, y - 1, z + 1);
-      }
-      if (lz) {
-        if (hx) mzx = at(x + 1, y, z - 1);
-        if (hy) mzy = at(x, y + 1, z - 1);
-      }
-      TvVec<V> acc;
-#pragma unroll
-      for (int c = 0; c < V; ++c) {
-        const float dx = fx.v[c] - t.v[c], dy = fy.v[c] - t.v[c], dz = fz.v[c] - t.v[c];
-        const float inv = tv_inv_norm(dx, dy, dz, eps);
-        const float px = dx * inv;
-        float a = (-px - dy * inv) - dz * inv;
-        if (x > 0) a += tx.v[c];
-        if (ly) {
-          const float e = t.v[c] - my.v[c];
-          a += e * tv_inv_norm(myx.v[c] - my.v[c], e, myz.v[c] - my.v[c], eps);
-        }
-        if (lz) {
-          const float e = t.v[c] - mz.v[c];
-          a += e * tv_inv_norm(mzx.v[c] - mz.v[c], mzy.v[c] - mz.v[c], e, eps);
-        }
-        tx.v[c] = px;
-        acc.v[c] = a;
-        if (SUMS) {
-          const float r = sqrtf(fmaf(dz, dz, fmaf(dy, dy, fmaf(dx, dx, eps))));
-          if (ch + c == 0) sum_d += r; else sum_f += r;
-        }
-      }
-      if (write) {  // (a channel whose weight is 0 keeps its bits; a tensor whose channels all have weight 0 is not touched)
-        float* p = dst + off(x, y, z);
-        TvVec<V> old = tv_load<V>(p);
-#pragma unroll
-        for (int c = 0; c < V; ++c)
-          if (w[c] != 0.0f) old.v[c] += w[c] * acc.v[c];
-        tv_store<V>(p, old);
-      }
-      t = fx, my = myx, mz = mzx;
-    }
-  }
-  if (SUMS) {  // sum of r per kind: wave -> workgroup -> one atomic add each (the sums are for logging; the gradient has no atomics)
-    __shared__ float s_part[2][kTvRows];
-    sum_d = wave_sum(sum_d);
-    sum_f = wave_sum(sum_f);
-    if (threadIdx.x == 0) s_part[0][threadIdx.y] = sum_d, s_part[1][threadIdx.y] = sum_f;
-    __syncthreads();
-    if (threadIdx.x == 0 && threadIdx.y == 0) {
-      float a = 0.0f, b = 0.0f;
-      for (int r = 0; r < kTvRows; ++r) a += s_part[0][r], b += s_part[1][r];
-      unsafeAtomicAdd(sums + 0, a);
-      unsafeAtomicAdd(sums + 1, b);
-    }
-  }
-}
-
-// =============================================================================================
-// rf_node_max_weight: per grid node the largest compositing weight any sample ever gave it.  The walk is
-// render_forward_ray's P0 without everything that depends on colour: one wave per ray, lanes = the samples of a 64-sample chunk, the
-// same helpers in the same order (load_ray, box_span / chunk_outside_box, z_of / sample_at, corners_of, the separately rounded density
-// sum in ATen's corner order, density_post, occupancy_alpha, the DPP transmittance scan), so w_i = alpha_i T_i is the forward's float
-// bit for bit.  No SH basis, no LDS work list, no cache.  Every corner k of an inside sample's cell offers v = w_i * cn.w[k] to
-// M[node]: an atomicMax on the bit pattern (integer order == float order for non-negative floats), behind a plain load that rejects
-// what cannot raise the entry -- a stale value read there is only ever too SMALL (entries never fall), which costs a redundant atomic
-// and never a wrong result.  A maximum does not depend on the order of arrival: bitwise reproducible.  M is in plain node order
-// ((x * Y + y) * Z + z) whatever the grid's storage.
-// GUARD / DEDUPE are measurement switches of tools/node_weights_time.py (compile-time: RF_NMW_GUARD, RF_NMW_DEDUPE).  DEDUPE: a
-// lane whose predecessor sampled the same cell and offers at least as much to a corner drops that corner's update (the relation is
-// transitive along a run of lanes, so the run's first lane still carries the maximum).
-// =============================================================================================
-#ifndef RF_NMW_GUARD
-#define RF_NMW_GUARD 1
-#endif
-#ifndef RF_NMW_DEDUPE
-#define RF_NMW_DEDUPE 0
-#endif
-
-template <bool GUARD, bool DEDUPE>
-__global__ __launch_bounds__(kBlock) void node_max_weight_kernel(GridArgs g, RayArgs r, uint32_t flags, unsigned int* M) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
-  if (ray >= r.n) return;  // (wave-uniform)
-
-  const RayState st = load_ray(r, g, ray, flags);
-  const bool use_occ = (flags & RF_FLAG_OCCUPANCY_SKIP) && g.occ != nullptr;
-  const BoxSpan span = box_span(st, r, g);
-  const unsigned int px = (unsigned)g.Y * (unsigned)g.Z, py = (unsigned)g.Z;  // plain node order of M
-  float T_carry = 1.0f;
-  const int nchunks = (r.S + kWave - 1) / kWave;
-  for (int chunk = 0; chunk < nchunks; ++chunk) {
-    if (chunk_outside_box(span, st, r, chunk)) continue;  // wave-uniform: sigma = 0 -> w = 0, T unchanged
-    const int s = chunk * kWave + lane;
-    const Sample sm = make_sample(st, r, g, ray, s);
-    bool live = sm.inside;
-    if (use_occ && live) live = cell_occupied(sm.cell, g);
-    float sigma = 0.0f;
-    Corners cn;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) cn.w[k] = 0.0f, cn.lin[k] = 0u;
-    cn.s[0] = cn.s[1] = cn.s[2] = 0u;
-    const uint32_t packed = pack_cell(sm.cell);
-    if (live) {
-      const float wts[6] = {sm.cell.w0[0], sm.cell.w1[0], sm.cell.w0[1], sm.cell.w1[1], sm.cell.w0[2], sm.cell.w1[2]};
-      cn = corners_of(packed, wts, g);
-      float pre;
-      sigma = interp_density(cn, g, pre);  // (reads element 0 of a node's density / base record only: no feature is touched)
-    }
-    float one_minus;
-    const float alpha = occupancy_alpha(sigma * sm.delta, one_minus);
-    float incl_e = sm.valid ? one_minus : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
-    wave_incl_scan_trans(incl_e, incl_a);
-    const float incl = prefix_transmittance(incl_e, incl_a);
-    const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
-    const float T = T_carry * excl;
-    const float w = live ? alpha * T : 0.0f;
-    T_carry = T_carry * read_lane(incl, kWave - 1);
-
-    // the cell's lower node in plain order; the steps collapse where corners_of's do (clamped at the border)
-    const int ix0 = (int)(packed & 0x7ffu) - 1, iy0 = (int)((packed >> 11) & 0x7ffu) - 1, iz0 = (int)(packed >> 22) - 1;
-    const unsigned int lin0 = ((unsigned)max(ix0, 0) * (unsigned)g.Y + (unsigned)max(iy0, 0)) * (unsigned)g.Z + (unsigned)max(iz0, 0);
-    const unsigned int sx = cn.s[0] ? px : 0u, sy = cn.s[1] ? py : 0u, sz = cn.s[2] ? 1u : 0u;
-    uint32_t prev_cell = 0u;
-    if constexpr (DEDUPE) {
-      const uint32_t tag = live ? packed : 0xffffffffu;  // (a live cell never packs to all ones: dims <= 2046)
-      prev_cell = (uint32_t)__builtin_amdgcn_update_dpp((int)0xfffffffeu, (int)tag, kDppWaveShr1, 0xf, 0xf, false);
-      prev_cell = (prev_cell == tag) ? 1u : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float v = w * cn.w[k];
-      bool offer = v > 0.0f;  // a product equal to 0 (or a NaN) updates nothing
-      if constexpr (DEDUPE) {
-        const float pv = dpp_move<kDppWaveShr1, 0xf>(0.0f, v);
-        offer = offer && !(prev_cell && pv >= v);
-      }
-      if (offer) {
-        unsigned int* p = M + (size_t)(lin0 + ((k & 1) ? sx : 0u) + ((k & 2) ? sy : 0u) + ((k & 4) ? sz : 0u));
-        if (!GUARD || v > __uint_as_float(*p)) atomicMax(p, __float_as_uint(v));
-      }
-    }
-    if (T_carry == 0.0f) break;  // every later weight is exactly 0
-  }
-}
-
-// =============================================================================================
-// rf_distortion: the distortion loss of a ray's compositing weights.  With the forward's samples and weights
-// w_i = T_i alpha_i (the walk of node_max_weight_kernel: same helpers, same order, no colour), s_i = (z_i - near) / (far - near) of the
-// batch's own bounds, and sample i standing for the interval it composites over (d_i = s_{i+1} - s_i, m_i = (s_i + s_{i+1}) / 2; the last
-// sample: d = 0, m = s):
-//   l = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
-// The m_i are sorted, so with the exclusive prefixes A_i = sum_{j<i} w_j, B_i = sum_{j<i} w_j m_j and the totals W, WM:
-//   l = 2 sum_i w_i (m_i A_i - B_i) + (1/3) sum_i w_i^2 d_i                                           (prefixes only: pass 1)
-//   e_i = dl/dw_i = 2 [ m_i (A_i - (W - A_i - w_i)) - (B_i - (WM - B_i - w_i m_i)) ] + (2/3) w_i d_i   (needs the totals: pass 2)
-//   dl/dsigma_i = delta_i ( T_{i+1} e_i - sum_{j>i} w_j e_j )      -- render_backward_kernel's adjoint with this e_i
-// One wave per ray, lanes = the samples of a 64-sample chunk.  Pass 1 walks near to far (stops where the carried T is exactly 0) and
-// leaves each chunk's (T, A, B) carry in a per-wave LDS stash; pass 2 (GRAD) walks far to near with a true running suffix sum,
-// evaluates each chunk again from its carry and scatters 8 float atomics per sample whose gradient is non-zero onto the density
-// element.  Chunks beyond the stash (S > 64 kDistStash) get their carry by walking forward again from the last stashed one: correct
-// for every S, quadratic only in the chunks above the capacity.
-// =============================================================================================
-constexpr int kDistStash = 16;  // chunks whose carry is kept in LDS: 1024 samples per ray
-
-// inclusive PREFIX sum over the wave (DPP: four row_shr steps inside each row of 16 lanes, row_bcast:15 / :31 fold the rows)
-__device__ __forceinline__ float wave_incl_scan_add(float x) {
-  x += dpp_move<kDppRowShr1, 0xf>(0.0f, x);
-  x += dpp_move<kDppRowShr2, 0xf>(0.0f, x);
-  x += dpp_move<kDppRowShr4, 0xf>(0.0f, x);
-  x += dpp_move<kDppRowShr8, 0xf>(0.0f, x);
-  x += dpp_move<kDppRowBcast15, 0xa>(0.0f, x);
-  x += dpp_move<kDppRowBcast31, 0xc>(0.0f, x);
-  return x;
-}
-
-struct DistCarry {
-  float T, A, B;  // transmittance in front of the chunk, sum of w and of w m over the samples in front of it
-};
-
-// everything one lane knows about its sample of a chunk, given the chunk's carry
-struct DistChunk {
-  float w, m, d, A, B;   // weight, interval mid-point and width, exclusive prefixes (carry included)
-  float delta, sigma, Tn;  // interval length, activated density, T_{i+1} = T_i exp(-sigma_i delta_i)
-  bool live;
-  Corners cn;
-  DistCarry next;  // the carry behind the chunk (wave-uniform)
-};
-
-__device__ __forceinline__ DistChunk dist_chunk(const GridArgs& g, const RayArgs& r, const RayState& st, long long ray, int chunk, int lane,
-                                                bool use_occ, float inv_span, const DistCarry& in) {
-  DistChunk c;
-  const int s = chunk * kWave + lane;
-  const float z = z_of(st, r, ray, s), zn = z_of(st, r, ray, s + 1);
-  const Sample sm = sample_at(st, r, g, s, z, zn);  // == make_sample
-  bool live = sm.inside;
-  if (use_occ && live) live = cell_occupied(sm.cell, g);
-  float sigma = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) c.cn.w[k] = 0.0f, c.cn.lin[k] = 0u;
-  c.cn.s[0] = c.cn.s[1] = c.cn.s[2] = 0u;
-  if (live) {
-    const float wts[6] = {sm.cell.w0[0], sm.cell.w1[0], sm.cell.w0[1], sm.cell.w1[1], sm.cell.w0[2], sm.cell.w1[2]};
-    c.cn = corners_of(pack_cell(sm.cell), wts, g);
-    float pre;
-    sigma = interp_density(c.cn, g, pre);
-  }
-  float E;
-  const float alpha = occupancy_alpha(sigma * sm.delta, E);
-  float incl_e = sm.valid ? E : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
-  wave_incl_scan_trans(incl_e, incl_a);
-  const float incl = prefix_transmittance(incl_e, incl_a);
-  const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
-  const float T = in.T * excl;
-  c.w = live ? alpha * T : 0.0f;
-  c.Tn = T * E;
-  c.delta = sm.delta;
-  c.sigma = sigma;
-  c.live = live;
-  // the interval of the sample on the batch's own [near, far] (the camera bounds, also under AABB sampling)
-  const float s0 = (z - r.near) * inv_span, s1 = (zn - r.near) * inv_span;
-  const bool last = s >= r.S - 1;
-  c.d = last ? 0.0f : s1 - s0;
-  c.m = last ? s0 : 0.5f * (s0 + s1);
-  const float wm = c.w * c.m;
-  const float iw = wave_incl_scan_add(c.w), iwm = wave_incl_scan_add(wm);
-  c.A = in.A + (iw - c.w);
-  c.B = in.B + (iwm - wm);
-  c.next.T = in.T * read_lane(incl, kWave - 1);
-  c.next.A = in.A + read_lane(iw, kWave - 1);
-  c.next.B = in.B + read_lane(iwm, kWave - 1);
-  return c;
-}
-
-template <bool GRAD>
-__global__ __launch_bounds__(kBlock) void distortion_kernel(GridArgs g, RayArgs r, uint32_t flags, float scale, const float* __restrict__ gloss,
-                                                            float* __restrict__ loss, float* __restrict__ gdens) {
-  __shared__ float s_stash[GRAD ? kWavesPerBlock : 1][kDistStash][3];
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
-  if (ray >= r.n) return;  // (wave-uniform)
-
-  float factor = scale;
-  if (GRAD && gloss) factor *= gloss[ray];
-  const bool want_grad = GRAD && factor != 0.0f;
-  if (!want_grad && !loss) return;
-
-  const RayState st = load_ray(r, g, ray, flags);
-  const bool use_occ = (flags & RF_FLAG_OCCUPANCY_SKIP) && g.occ != nullptr;
-  const BoxSpan span = box_span(st, r, g);
-  const float inv_span = 1.0f / (r.far - r.near);
-  const int nchunks = (r.S + kWave - 1) / kWave;
-
-  // pass 1, near to far: the loss from prefixes, the totals, every chunk's carry
-  DistCarry carry = {1.0f, 0.0f, 0.0f};
-  float part = 0.0f;  // this lane's share of l
-  int last_chunk = -1;
-  for (int chunk = 0; chunk < nchunks; ++chunk) {
-    if (GRAD && chunk < kDistStash && lane == 0) {
-      s_stash[wave][chunk][0] = carry.T;
-      s_stash[wave][chunk][1] = carry.A;
-      s_stash[wave][chunk][2] = carry.B;
-    }
-    if (chunk_outside_box(span, st, r, chunk)) continue;  // wave-uniform: w = 0 for the whole chunk, the carry unchanged
-    const DistChunk c = dist_chunk(g, r, st, ray, chunk, lane, use_occ, inv_span, carry);
-    part += 2.0f * c.w * (c.m * c.A - c.B) + (1.0f / 3.0f) * (c.w * c.w) * c.d;
-    carry = c.next;
-    last_chunk = chunk;
-    if (carry.T == 0.0f) break;  // every later weight is exactly 0
-  }
-  if (loss) {
-    const float total = wave_sum(part);
-    if (lane == 0) loss[ray] = total;
-  }
-  if (!want_grad) return;
-  if constexpr (GRAD) {
-    wave_lds_fence();
-    const float W = carry.A, WM = carry.B;
-    float suffix = 0.0f;  // sum of w_j e_j over all samples beyond the current chunk
-    // pass 2, far to near
-    for (int chunk = last_chunk; chunk >= 0; --chunk) {
-      if (chunk_outside_box(span, st, r, chunk)) continue;
-      const int have = min(chunk, kDistStash - 1);
-      DistCarry in = {s_stash[wave][have][0], s_stash[wave][have][1], s_stash[wave][have][2]};
-      for (int k = have; k < chunk; ++k) {  // beyond the stash: walk forward again from the last stashed carry
-        if (chunk_outside_box(span, st, r, k)) continue;
-        in = dist_chunk(g, r, st, ray, k, lane, use_occ, inv_span, in).next;
-      }
-      const DistChunk c = dist_chunk(g, r, st, ray, chunk, lane, use_occ, inv_span, in);
-      const float wm = c.w * c.m;
-      const float e = 2.0f * (c.m * (c.A - ((W - c.A) - c.w)) - (c.B - ((WM - c.B) - wm))) + (2.0f / 3.0f) * (c.w * c.d);
-      const float we = c.w * e;  // (0 for lanes beyond the ray's last sample and for samples outside the box: w = 0)
-      const float incl = wave_incl_rscan_add(we, lane);
-      const float after = (incl - we) + suffix;  // sum over samples strictly behind this one
-      suffix += __shfl(incl, 0, kWave);
-      const float g_sigma = c.delta * (c.Tn * e - after);
-      float g_pre;
-      if (g.mode == RF_DENSITY_RELU)
-        g_pre = (c.sigma > 0.0f) ? g_sigma : 0.0f;
-      else if (g.mode == RF_DENSITY_SOFTPLUS)
-        g_pre = g_sigma * softplus_slope(c.sigma);
-      else
-        g_pre = g_sigma;
-      g_pre *= factor;
-      if (c.live && g_pre != 0.0f) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          // (a corner outside the grid has weight 0 and the clamped index of a real node: nothing is added, nothing out of range is read)
-          const size_t at = (size_t)c.cn.lin[k] * (size_t)g.dstride;
-          float gv = (c.cn.w[k] * g_pre) * g.rho;
-          if (g.mode == RF_DENSITY_ABS) {
-            const float dv = g.dens[at] * g.rho;
-            gv = (dv > 0.f) ? gv : ((dv < 0.f) ? -gv : 0.0f);
-          }
-          if (gv != 0.0f) unsafeAtomicAdd(gdens + at, gv);
-        }
-      }
-    }
-  }
-}
-
-// =============================================================================================
-// rf_render_geometry: surface normals and quantile depth of the rendered rays.  The walk of
-// node_max_weight_kernel once more -- one wave per ray, lanes = the samples of a 64-sample chunk, the same helpers in the same order, so
-// w_i = alpha_i T_i is the forward's float bit for bit -- compositing three per-sample quantities:
-//   acc = sum_i w_i                    per-lane partial sums over the chunks, one wave sum at the end: render_forward_ray's order and bits
-//   N   = sum_i w_i n_i                n_i = -g_i / |g_i| (0 where g_i = 0), g_i the world-space gradient of the interpolated
-//                                      pre-activation density at the sample; per-lane products, a wave sum per chunk, a carry: no atomics
-//   z_q = z of the first sample with 1 - T_{i+1} >= quantile (0 if none): a ballot over the chunk and its first set lane
-// The gradient needs the 8 corner values themselves, not only their weighted sum: interp_density_values is interp_density (same
-// loads, same sum, same activation) handing them back.  No feature is read, nothing is written but one result per ray.
-// =============================================================================================
-__device__ __forceinline__ float interp_density_values(const Corners& c, const GridArgs& g, float v[8]) {
-  float raw[8];
-  if (g.near32) {  // (wave-uniform)
-    const unsigned int sb = (unsigned int)g.dstride * 4u;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const unsigned int o = __umul24(c.lin[k], sb);
-      raw[k] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(g.dens) + (size_t)o);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) raw[k] = g.dens[c.lin[k] * g.dstride];
-    asm volatile("" ::: "memory");  // (keeps the two branches' loads apart: merged, they lose the scalar-base addressing)
-  }
-  float acc = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    v[k] = raw[k] * g.rho;
-    if (g.mode == RF_DENSITY_ABS) v[k] = fabsf(v[k]);
-    acc = acc + v[k] * c.w[k];
-  }
-  if (g.mode == RF_DENSITY_RELU) return fmaxf(acc, 0.0f);
-  if (g.mode == RF_DENSITY_SOFTPLUS) return (acc > 20.0f) ? acc : log1pf(expf(acc));
-  return acc;
-}
-
-__global__ __launch_bounds__(kBlock) void render_geometry_kernel(GridArgs g, RayArgs r, uint32_t flags, float quantile, float* __restrict__ normal,
-                                                                 float* __restrict__ qdepth, float* __restrict__ acc_out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const long long ray = (long long)blockIdx.x * kWavesPerBlock + wave;
-  if (ray >= r.n) return;  // (wave-uniform)
-
-  const RayState st = load_ray(r, g, ray, flags);
-  const bool use_occ = (flags & RF_FLAG_OCCUPANCY_SKIP) && g.occ != nullptr;
-  const BoxSpan span = box_span(st, r, g);
-  // d idx_a / d p_a (locate): world gradient = index gradient * dims_a * norm_scale_a / 2
-  const float gscale[3] = {((float)g.X * g.nscale[0]) * 0.5f, ((float)g.Y * g.nscale[1]) * 0.5f, ((float)g.Z * g.nscale[2]) * 0.5f};
-  float T_carry = 1.0f, part_acc = 0.0f, zq = 0.0f;
-  float N[3] = {0.0f, 0.0f, 0.0f};
-  bool found = false;  // (wave-uniform)
-  const int nchunks = (r.S + kWave - 1) / kWave;
-  for (int chunk = 0; chunk < nchunks; ++chunk) {
-    if (chunk_outside_box(span, st, r, chunk)) continue;  // wave-uniform: sigma = 0 -> w = 0, T unchanged
-    const int s = chunk * kWave + lane;
-    const Sample sm = make_sample(st, r, g, ray, s);
-    bool live = sm.inside;
-    if (use_occ && live) live = cell_occupied(sm.cell, g);
-    float sigma = 0.0f;
-    float v[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = 0.0f;
-    const uint32_t packed = pack_cell(sm.cell);
-    if (live) {
-      const float wts[6] = {sm.cell.w0[0], sm.cell.w1[0], sm.cell.w0[1], sm.cell.w1[1], sm.cell.w0[2], sm.cell.w1[2]};
-      const Corners cn = corners_of(packed, wts, g);
-      sigma = interp_density_values(cn, g, v);  // (reads element 0 of a node's density / base record only: no feature is touched)
-    }
-    float one_minus;
-    const float alpha = occupancy_alpha(sigma * sm.delta, one_minus);
-    float incl_e = sm.valid ? one_minus : 1.0f, incl_a = sm.valid ? alpha : 0.0f;
-    wave_incl_scan_trans(incl_e, incl_a);
-    const float incl = prefix_transmittance(incl_e, incl_a);
-    const float excl = dpp_move<kDppWaveShr1, 0xf>(1.0f, incl);  // lane i <- lane i-1, lane 0 <- 1
-    const float T = T_carry * excl;
-    const float wf = alpha * T;  // the forward's w (alpha = 0 where the sample is not live)
-    if (sm.valid) part_acc += wf;
-    const float w = live ? wf : 0.0f;
-
-    // quantile depth: C_i = 1 - T_{i+1}, T_{i+1} the transmittance the next sample is weighted with
-    if (!found) {
-      const float C = 1.0f - T_carry * incl;
-      const unsigned long long hit = __ballot(sm.valid && C >= quantile);
-      if (hit) {
-        found = true;
-        zq = read_lane(sm.z, __builtin_amdgcn_readfirstlane(__ffsll((long long)hit) - 1));
-      }
-    }
-    T_carry = T_carry * read_lane(incl, kWave - 1);
-
-    // index-space gradient of the trilinear interpolant: a corner outside the grid counts as 0 (corners_of masks its weight)
-    const int ix0 = (int)(packed & 0x7ffu) - 1, iy0 = (int)((packed >> 11) & 0x7ffu) - 1, iz0 = (int)(packed >> 22) - 1;
-    const bool okx[2] = {ix0 >= 0, ix0 + 1 < g.X}, oky[2] = {iy0 >= 0, iy0 + 1 < g.Y}, okz[2] = {iz0 >= 0, iz0 + 1 < g.Z};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (okx[k & 1] && oky[(k >> 1) & 1] && okz[k >> 2]) ? v[k] : 0.0f;
-    const float* w0 = sm.cell.w0;
-    const float* w1 = sm.cell.w1;
-    const float wyz[4] = {w0[1] * w0[2], w1[1] * w0[2], w0[1] * w1[2], w1[1] * w1[2]};  // [dy + 2 dz]
-    const float wxz[4] = {w0[0] * w0[2], w1[0] * w0[2], w0[0] * w1[2], w1[0] * w1[2]};  // [dx + 2 dz]
-    const float wxy[4] = {w0[0] * w0[1], w1[0] * w0[1], w0[0] * w1[1], w1[0] * w1[1]};  // [dx + 2 dy]
-    float gw[3];
-    gw[0] = (((v[1] - v[0]) * wyz[0] + (v[3] - v[2]) * wyz[1]) + ((v[5] - v[4]) * wyz[2] + (v[7] - v[6]) * wyz[3])) * gscale[0];
-    gw[1] = (((v[2] - v[0]) * wxz[0] + (v[3] - v[1]) * wxz[1]) + ((v[6] - v[4]) * wxz[2] + (v[7] - v[5]) * wxz[3])) * gscale[1];
-    gw[2] = (((v[4] - v[0]) * wxy[0] + (v[5] - v[1]) * wxy[1]) + ((v[6] - v[2]) * wxy[2] + (v[7] - v[3]) * wxy[3])) * gscale[2];
-    // n = -g / |g|, scaled by the largest component first (neither the squares of a huge gradient nor those of a tiny one leave float32)
-    const float big = fmaxf(fmaxf(fabsf(gw[0]), fabsf(gw[1])), fabsf(gw[2]));
-    float part[3] = {0.0f, 0.0f, 0.0f};
-    if (w != 0.0f && big > 0.0f) {  // a sample without weight contributes nothing, whatever its gradient
-      const float u[3] = {gw[0] / big, gw[1] / big, gw[2] / big};
-      const float len = sqrtf((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]);
-#pragma unroll
-      for (int a = 0; a < 3; ++a) part[a] = w * -(u[a] / len);
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) N[a] += wave_sum(part[a]);
-    if (T_carry == 0.0f) break;  // every later weight is exactly 0 (and 1 - T reached 1: the quantile is found)
-  }
-  const float acc = wave_sum(part_acc);
-  if (lane == 0) {
-    if (normal) normal[ray * 3 + 0] = N[0], normal[ray * 3 + 1] = N[1], normal[ray * 3 + 2] = N[2];
-    if (qdepth) qdepth[ray] = zq;
-    if (acc_out) acc_out[ray] = acc;
-  }
-}
-
-// rf_prune_grid: keep(n) = some node m of the grid with |m - n|_inf <= dilate has M[m] > threshold; a pruned node's raw density
-// is lowered to the fill.  GATHER form: one thread owns a node, reads the (2 dilate + 1)^3 neighbourhood of M (plain node order,
-// clipped to the grid) and writes only its own density element (node_lin: padding nodes of bricked storage are never addressed).
-// The two counters take one atomic add per wave.
-__global__ __launch_bounds__(256) void prune_grid_kernel(GridArgs g, const float* __restrict__ M, float threshold, int dilate, float fill,
-                                                         float* __restrict__ dens, unsigned char* __restrict__ keep_out,
-                                                         unsigned long long* __restrict__ counts, long long nodes) {
-  const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool real = n < nodes;
-  bool keep = false;
-  if (real) {
-    const int z = (int)(n % g.Z), y = (int)((n / g.Z) % g.Y), x = (int)(n / ((long long)g.Z * g.Y));
-    const int x0 = max(x - dilate, 0), x1 = min(x + dilate, g.X - 1), y0 = max(y - dilate, 0), y1 = min(y + dilate, g.Y - 1);
-    const int z0 = max(z - dilate, 0), z1 = min(z + dilate, g.Z - 1);
-    for (int xi = x0; xi <= x1 && !keep; ++xi)
-      for (int yi = y0; yi <= y1 && !keep; ++yi) {
-        const float* row = M + ((long long)xi * g.Y + yi) * g.Z;
-        for (int zi = z0; zi <= z1; ++zi) keep = keep || row[zi] > threshold;
-      }
-    if (keep_out) keep_out[n] = keep ? 1 : 0;
-    if (!keep) {
-      float* p = dens + (long long)node_lin(g, x, y, z) * g.dstride;
-      const float D = *p;
-      if (g.mode == RF_DENSITY_ABS) {
-        *p = 0.0f;
-      } else if (fill < D) {  // min(D, fill): pruning never raises a density (a density at or below the fill keeps its bits)
-        *p = fill;
-      }
-    }
-  }
-  if (counts) {
-    const unsigned long long kept = __popcll(__ballot(real && keep)), pruned = __popcll(__ballot(real && !keep));
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-      if (kept) atomicAdd(counts + 0, kept);
-      if (pruned) atomicAdd(counts + 1, pruned);
-    }
-  }
-}
-
-// rf_node_bounds: the index box of the nodes whose OWN activated density sigma_n = post(pre(D_n * rho)) exceeds the threshold (no
-// interpolation), merged into bounds[0..2] (min) / bounds[3..5] (max), and their number added to count[0].  One thread per node, z
-// fastest; only a node's density element is read (node_lin: padding nodes of bricked storage are never addressed).  A wave whose
-// ballot is empty does nothing; otherwise its six values are reduced with xor shuffles (lanes that do not pass carry the neutral
-// elements) and lane 0 issues six int32 atomicMin / atomicMax and one 64-bit add.  Integer atomics: the result does not depend on
-// the order of arrival.
-__global__ __launch_bounds__(256) void node_bounds_kernel(GridArgs g, float threshold, int* __restrict__ bounds,
-                                                          unsigned long long* __restrict__ count, long long nodes) {
-  const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
-  bool pass = false;
-  if (n < nodes) {
-    const int z = (int)(n % g.Z), y = (int)((n / g.Z) % g.Y), x = (int)(n / ((long long)g.Z * g.Y));
-    float pre = g.dens[(long long)node_lin(g, x, y, z) * g.dstride] * g.rho;
-    if (g.mode == RF_DENSITY_ABS) pre = fabsf(pre);
-    pass = density_post(pre, g.mode) > threshold;
-    if (pass) {
-      lo[0] = hi[0] = x;
-      lo[1] = hi[1] = y;
-      lo[2] = hi[2] = z;
-    }
-  }
-  const unsigned long long ballot = __ballot(pass);
-  if (ballot == 0ull) return;  // (wave-uniform)
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      lo[a] = min(lo[a], __shfl_xor(lo[a], off, kWave));
-      hi[a] = max(hi[a], __shfl_xor(hi[a], off, kWave));
-    }
-  }
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      atomicMin(bounds + a, lo[a]);
-      atomicMax(bounds + 3 + a, hi[a]);
-    }
-    if (count) atomicAdd(count, (unsigned long long)__popcll(ballot));
-  }
-}
-
-// rf_resample_grid: the RAW [F+1]-channel volume of `src` seen from another lattice.  Destination node i on axis a sits at the
-// continuous source index s_a = fma(scale_a, i_a, offset_a); a node with some s_a outside [-0.5, n_a - 0.5] (the source BOX: nodes are
-// voxel centres) is (fill, 0 ...), any other takes the trilinear sum of the 8 corners of its cell with s_a clamped to [0, n_a - 1],
-// i0 = min(floor(s), n - 1), i1 = min(i0 + 1, n - 1), lambda = s - i0.  No density scale, no activation.  The thread shape of
-// upsample_grid_kernel: one thread per (destination node, channel), channel fastest, any storage on either side.
-// SUMMATION ORDER (fixed, part of the contract): corner k = dx * 4 + dy * 2 + dz ascending, weight (wx * wy) * wz,
-// v = val[0] * w[0], then v = fma(val[k], w[k], v) for k = 1 .. 7.  With scale 1 and an integer offset every weight is exactly 1 or 0:
-// a bit-exact copy of finite values.
-struct ResampleAxis {
-  int i0, i1;
-  float w0, w1;
-  bool outside;
-};
-__device__ __forceinline__ ResampleAxis resample_axis(int dst, int in_size, float scale, float offset) {
-  float s = fmaf(scale, (float)dst, offset);
-  ResampleAxis a;
-  a.outside = s < -0.5f || s > (float)in_size - 0.5f;
-  s = fminf(fmaxf(s, 0.0f), (float)(in_size - 1));
-  a.i0 = min((int)floorf(s), in_size - 1);
-  a.i1 = min(a.i0 + 1, in_size - 1);
-  const float lambda = s - (float)a.i0;
-  a.w0 = 1.0f - lambda;
-  a.w1 = lambda;
-  return a;
-}
-
-struct ResampleMap {
-  float scale[3], offset[3];
-};
-
-__global__ __launch_bounds__(256) void resample_grid_kernel(GridArgs src, GridArgs dst, ResampleMap m, float fill, float* dst_first,
-                                                            float* dst_second, long long total) {
-  const int C = dst.F + 1, K = dst.F / 3;
-  for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
-    const int ch = (int)(it % C);
-    long long node = it / C;
-    const int z = (int)(node % dst.Z);
-    node /= dst.Z;
-    const int y = (int)(node % dst.Y), x = (int)(node / dst.Y);
-    const ResampleAxis ax = resample_axis(x, src.X, m.scale[0], m.offset[0]), ay = resample_axis(y, src.Y, m.scale[1], m.offset[1]),
-                       az = resample_axis(z, src.Z, m.scale[2], m.offset[2]);
-    float v;
-    if (ax.outside || ay.outside || az.outside) {
-      v = ch == 0 ? fill : 0.0f;
-    } else {
-      auto at = [&](int xi, int yi, int zi) -> float {
-        bool first;
-        const long long off = channel_offset(src, node_lin(src, xi, yi, zi), ch, K, first);
-        return (first ? src.dens : src.feat)[off];
-      };
-      float val[8], wgt[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int dx = k >> 2, dy = (k >> 1) & 1, dz = k & 1;
-        val[k] = at(dx ? ax.i1 : ax.i0, dy ? ay.i1 : ay.i0, dz ? az.i1 : az.i0);
-        wgt[k] = ((dx ? ax.w1 : ax.w0) * (dy ? ay.w1 : ay.w0)) * (dz ? az.w1 : az.w0);
-      }
-      v = val[0] * wgt[0];
-#pragma unroll
-      for (int k = 1; k < 8; ++k) v = fmaf(val[k], wgt[k], v);
-    }
-    bool first;
-    const long long off = channel_offset(dst, node_lin(dst, x, y, z), ch, K, first);
-    (first ? dst_first : dst_second)[off] = v;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// host side of the C ABI
-// ---------------------------------------------------------------------------------------------
-// split / bricked storage at SH degree 0 keeps all four channels in the first tensor: the second tensor -- parameters or
-// gradients -- may then be null
-bool second_tensor_optional(const RFGrid* g) { return g->layout != RF_LAYOUT_REFERENCE && g->num_features == 3; }
-
-// the node count, every axis padded to whole 8-node bricks where `whole_bricks` says so
-unsigned long long node_count(const RFGrid* g, bool whole_bricks) {
-  unsigned long long nodes = 1;
-  for (int a = 0; a < 3; ++a) nodes *= (unsigned long long)(whole_bricks ? (g->dims[a] + 7) / 8 * 8 : g->dims[a]);
-  return nodes;
-}
-
-// an A/B switch of the environment as an integer (`fallback` when unset); the callers that read one once per process keep it in a static
-int env_int(const char* name, int fallback) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : fallback;
-}
-bool env_flag(const char* name, bool fallback) { return env_int(name, fallback) != 0; }
-
-int check_grid(const RFGrid* g) {
-  if (!g || !g->densities_dev) return RF_ERR_NULL_POINTER;
-  if (!g->features_dev && !second_tensor_optional(g)) return RF_ERR_NULL_POINTER;
-  for (int a = 0; a < 3; ++a)
-    if (g->dims[a] < 1 || g->dims[a] > 2046) return RF_ERR_BAD_SHAPE;
-  const int F = g->num_features;
-  if (!(F == 3 || F == 12 || F == 27 || F == 48)) return RF_ERR_UNSUPPORTED;  // SH degree 0..3
-  if (g->density_mode < RF_DENSITY_RELU || g->density_mode > RF_DENSITY_IDENTITY) return RF_ERR_UNSUPPORTED;
-  if (g->layout == RF_LAYOUT_REFERENCE) {
-    if (g->density_stride < 1 || g->feature_stride < F) return RF_ERR_BAD_SHAPE;
-  } else if (g->layout == RF_LAYOUT_SPLIT || g->layout == RF_LAYOUT_BRICKED) {
-    if (g->density_stride < 4 || (F > 3 && g->feature_stride < F - 3)) return RF_ERR_BAD_SHAPE;
-  } else {
-    return RF_ERR_UNSUPPORTED;
-  }
-  // node indices are 32-bit in the kernels (node_lin: 24-bit multiplies into an unsigned int; element offsets are 64-bit):
-  // the node count, padded to whole bricks for the bricked order, must stay below 2^32
-  if (node_count(g, g->layout == RF_LAYOUT_BRICKED) >= (1ull << 32)) return RF_ERR_BAD_SHAPE;
-  return RF_OK;
-}
-
-GridArgs to_args(const RFGrid* g) {
-  GridArgs a;
-  a.dens = g->densities_dev;
-  a.feat = g->features_dev;
-  a.occ = g->occupancy_dev;
-  a.X = g->dims[0];
-  a.Y = g->dims[1];
-  a.Z = g->dims[2];
-  a.F = g->num_features;
-  a.dstride = g->density_stride;
-  a.fstride = g->feature_stride;
-  for (int i = 0; i < 3; ++i) {
-    a.amin[i] = g->aabb_min[i];
-    a.amax[i] = g->aabb_max[i];
-    a.nscale[i] = g->norm_scale[i];
-    a.nbias[i] = g->norm_bias[i];
-  }
-  a.rho = g->density_scale;
-  a.mode = g->density_mode;
-  a.layout = g->layout == RF_LAYOUT_REFERENCE ? RF_LAYOUT_REFERENCE : RF_LAYOUT_SPLIT;  // channel arrangement
-  a.bricked = g->layout == RF_LAYOUT_BRICKED;
-  a.nby = (a.Y + 7) / 8;
-  a.nbz = (a.Z + 7) / 8;
-  if (a.bricked) {
-    a.step[0] = 64u;
-    a.step[1] = 8u;
-    a.step[2] = 1u;
-    a.jump[0] = (unsigned)a.nby * (unsigned)a.nbz * 512u - 7u * 64u;
-    a.jump[1] = (unsigned)a.nbz * 512u - 7u * 8u;
-    a.jump[2] = 512u - 7u;
-  } else {
-    a.step[0] = a.jump[0] = (unsigned)a.Y * (unsigned)a.Z;
-    a.step[1] = a.jump[1] = (unsigned)a.Z;
-    a.step[2] = a.jump[2] = 1u;
-  }
-  {
-    const unsigned long long nodes = node_count(g, a.bricked);
-    const unsigned long long db = (unsigned long long)a.dstride * 4ull, fb = (unsigned long long)a.fstride * 4ull;
-    const uintptr_t d0 = reinterpret_cast<uintptr_t>(a.dens), f0 = a.feat ? reinterpret_cast<uintptr_t>(a.feat) : d0;
-    const uintptr_t lo = d0 < f0 ? d0 : f0;
-    const unsigned long long dend = (d0 - lo) + nodes * db, fend = a.feat ? (f0 - lo) + nodes * fb : 0ull;
-    const unsigned long long span = (dend > fend ? dend : fend) + 16ull;
-    a.base = reinterpret_cast<const char*>(lo);
-    a.dens_off = (unsigned int)(d0 - lo);
-    a.feat_off = (unsigned int)(f0 - lo);
-    a.near32 = nodes <= (1ull << 24) && db < (1ull << 24) && fb < (1ull << 24) && span < (1ull << 32);
-    // ($RF_FAR_ADDRESSING=1: the general 64-bit path on grids that would not need it -- tests compare the two)
-    a.near32 = a.near32 && env_int("RF_FAR_ADDRESSING", 0) == 0;
-  }
-  return a;
-}
-
-int check_rays(const RFRayBatch* r) {
-  if (!r) return RF_ERR_NULL_POINTER;
-  if (r->num_rays < 0 || r->num_samples < 1) return RF_ERR_BAD_SHAPE;
-  if (r->num_rays > 0 && !r->t_vals_dev) return RF_ERR_NULL_POINTER;
-  if (r->num_rays > 0 && !r->camera && (!r->origins_dev || !r->directions_dev)) return RF_ERR_NULL_POINTER;
-  if (r->camera) {
-    if (r->camera->height < 1 || r->camera->width < 1 || r->first_ray < 0) return RF_ERR_BAD_SHAPE;
-    if (r->first_ray + r->num_rays > (int64_t)r->camera->height * r->camera->width) return RF_ERR_BAD_SHAPE;
-  }
-  return RF_OK;
-}
-
-RayArgs to_args(const RFRayBatch* r, uint32_t flags = 0);
-RayArgs to_args(const RFRayBatch* r, uint32_t flags) {
-  RayArgs a;
-  a.origins = r->origins_dev;
-  a.directions = r->directions_dev;
-  a.n = r->num_rays;
-  a.S = r->num_samples;
-  a.near = r->near;
-  a.far = r->far;
-  a.tvals = r->t_vals_dev;
-  a.trand = r->t_rand_dev;
-  a.jkey = r->jitter_key;
-  a.ray0 = r->first_ray;
-  a.jitter = (flags & RF_FLAG_JITTER_KEYED) && !r->t_rand_dev;
-  a.cam = r->camera != nullptr;
-  a.H = a.W = 1;
-  a.focal = 1.0f;
-  for (int i = 0; i < 12; ++i) a.pose[i] = 0.0f;
-  if (r->camera) {
-    a.H = r->camera->height;
-    a.W = r->camera->width;
-    a.focal = r->camera->focal;
-    for (int i = 0; i < 12; ++i) a.pose[i] = r->camera->pose[i];
-  }
-  return a;
-}
-
-OutArgs to_args(const RFRenderOut* o) {
-  OutArgs a;
-  a.colour = o->colour_dev;
-  a.depth = o->depth_dev;
-  a.acc = o->acc_dev;
-  a.disparity = o->disparity_dev;
-  a.cache = o->sample_cache_dev;
-  a.tcache = o->trans_cache_dev;
-  a.cmask = reinterpret_cast<unsigned long long*>(o->chunk_mask_dev);
-  a.stop = o->stop_cache_dev;
-  a.hist = nullptr;
-  a.brick_shift = 0;
-  a.nby = a.nbz = 0;
-  return a;
-}
-
-int launch_status() { return hipGetLastError() == hipSuccess ? RF_OK : RF_ERR_LAUNCH; }
-
-// The one place that turns the SH degree into a kernel instantiation: f(std::integral_constant<int, K>) for the K = (degree + 1)^2
-// coefficients per colour of the grid, if K is in the set the caller allows -- the set is what gets instantiated; RF_ERR_UNSUPPORTED
-// otherwise.  f returns the call's return code.
-template <int... Ks>
-struct ShSet {};
-using ShAll = ShSet<1, 4, 9, 16>;
-using ShEven = ShSet<1, 9>;  // SH degree 0 / 2: 3 K + 1 channels are whole float4s
-template <int... Ks, class F>
-int dispatch_sh(int K, ShSet<Ks...>, F&& f) {
-  int rc = RF_ERR_UNSUPPORTED;
-  (void)(... || (K == Ks && ((rc = f(std::integral_constant<int, Ks>{})), true)));
-  return rc;
-}
-
-// the render kernels <K, DIFFUSE>: a render_diffuse pass reads one coefficient per colour, like SH degree 0
-template <class F>
-int dispatch_render(int K, bool diffuse, F&& f) {
-  if (diffuse || K == 1) return f(std::integral_constant<int, 1>{}, std::true_type{});
-  return dispatch_sh(K, ShSet<4, 9, 16>{}, [&](auto k) { return f(k, std::false_type{}); });
-}
-
-unsigned grid_1d(long long n, int block, long long cap = 256LL * 16) {
-  long long b = (n + block - 1) / block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (unsigned)b;
-}
-
 }  // namespace
-
 
 extern "C" {
 
@@ -5471,9 +3249,6 @@ static int brick_geometry(const RFGrid* grid, int brick_size, int* shift, int nb
   return (total * 8 - 1 <= (short_keys ? 0x7fffLL : (1LL << 21) - 1)) ? RF_OK : RF_ERR_UNSUPPORTED;
 }
 
-// the sample cache of a saving forward render: all four arrays or none
-static bool has_caches(const RFRenderOut* o) { return o->sample_cache_dev && o->trans_cache_dev && o->stop_cache_dev && o->chunk_mask_dev; }
-
 // RFRenderOut.key_hist_dev: the forward render counts the records of the binned backward per (brick, flags) key
 static int set_key_hist(const RFGrid* grid, const RFRenderOut* out, OutArgs* o) {
   int shift, nb[3];
@@ -5501,12 +3276,6 @@ static int emit_direct_args(const RFGrid* grid, int32_t brick_size, int32_t* cur
   gr->nby = nb[1];
   gr->nbz = nb[2];
   return RF_OK;
-}
-
-static void set_grads(const RFRenderGrads* grads, GradArgs* gr) {
-  gr->gcolour = grads->grad_colour_dev;
-  gr->gdepth = grads->grad_depth_dev;
-  gr->gacc = grads->grad_acc_dev;
 }
 
 // the two renders of a training iteration go into one launch when they cover the same rays, [0] specular and [1] render_diffuse
@@ -5567,7 +3336,7 @@ int rf_render_forward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags
     rc = set_key_hist(grid, out, &o);
     if (rc != RF_OK) return rc;
   }
-  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
+  const unsigned blocks = ray_blocks(rays->num_rays);
   hipStream_t st = (hipStream_t)stream;
   const bool diffuse = flags & RF_FLAG_RENDER_DIFFUSE;
   const int K = grid->num_features / 3;
@@ -5685,7 +3454,7 @@ static int backward_impl(const RFGrid* grid, const RFRayBatch* rays, uint32_t fl
   const RayArgs r = to_args(rays, flags);
   const OutArgs o = to_args(fwd);
   set_grads(grads, &gr);
-  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
+  const unsigned blocks = ray_blocks(rays->num_rays);
   hipStream_t st = (hipStream_t)stream;
   return dispatch_render(grid->num_features / 3, flags & RF_FLAG_RENDER_DIFFUSE, [&](auto k, auto d) {
     constexpr int K = decltype(k)::value;
@@ -5709,7 +3478,6 @@ int rf_render_backward(const RFGrid* grid, const RFRayBatch* rays, uint32_t flag
   gr.gfeat = grad_features_dev;
   return backward_impl(grid, rays, flags, fwd, grads, gr, stream);
 }
-
 
 int rf_render_backward_emit(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, const RFRenderOut* fwd,
                             const RFRenderGrads* grads, int32_t brick_size, int16_t* keys_dev, float* records_dev,
@@ -6091,301 +3859,6 @@ int rf_brick_accumulate_adam_split(const RFGrid* grid, int32_t brick_size, const
   req.scratch = scratch_dev;
   req.scratch_bytes = scratch_bytes;
   return brick_accumulate_impl(grid, brick_size, lists, num_lists, req, stream);
-}
-
-int rf_grid_query(const RFGrid* grid, const float* points_dev, int64_t num_points, float* out_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (num_points == 0) return RF_OK;
-  if (!points_dev || !out_dev) return RF_ERR_NULL_POINTER;
-  if (num_points < 0) return RF_ERR_BAD_SHAPE;
-  const GridArgs g = to_args(grid);
-  const long long total = (long long)num_points * (g.F + 1);
-  hipLaunchKernelGGL(grid_query_kernel, dim3(grid_1d(total, 256)), dim3(256), 0, (hipStream_t)stream, g, points_dev,
-                     (long long)num_points, out_dev);
-  return launch_status();
-}
-
-int rf_grid_query_backward(const RFGrid* grid, const float* points_dev, int64_t num_points, const float* grad_out_dev,
-                           float* grad_densities_dev, float* grad_features_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (num_points == 0) return RF_OK;
-  if (!points_dev || !grad_out_dev || !grad_densities_dev) return RF_ERR_NULL_POINTER;
-  if (!grad_features_dev && !second_tensor_optional(grid)) return RF_ERR_NULL_POINTER;
-  if (num_points < 0) return RF_ERR_BAD_SHAPE;
-  const GridArgs g = to_args(grid);
-  const long long total = (long long)num_points * (g.F + 1);
-  hipLaunchKernelGGL(grid_query_backward_kernel, dim3(grid_1d(total, 256)), dim3(256), 0, (hipStream_t)stream, g,
-                     points_dev, (long long)num_points, grad_out_dev, grad_densities_dev, grad_features_dev);
-  return launch_status();
-}
-
-int rf_grid_query_backward_points(const RFGrid* grid, const float* points_dev, int64_t num_points, const float* grad_out_dev,
-                                  float* grad_points_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (num_points < 0) return RF_ERR_BAD_SHAPE;
-  if (num_points == 0) return RF_OK;
-  if (!points_dev || !grad_out_dev || !grad_points_dev) return RF_ERR_NULL_POINTER;
-  if (!grid->features_dev && grid->num_features > 3) return RF_ERR_NULL_POINTER;
-  const GridArgs g = to_args(grid);
-  hipLaunchKernelGGL(grid_query_backward_points_kernel, dim3(grid_1d(num_points, 256)), dim3(256), 0, (hipStream_t)stream, g, points_dev,
-                     (long long)num_points, grad_out_dev, grad_points_dev);
-  return launch_status();
-}
-
-int rf_render_backward_rays(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, const RFRenderOut* fwd, const RFRenderGrads* grads,
-                            float* grad_origins_dev, float* grad_directions_dev, void* stream) {
-  int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  rc = check_rays(rays);
-  if (rc != RF_OK) return rc;
-  if (!fwd || !grads) return RF_ERR_NULL_POINTER;
-  if (rays->camera) return RF_ERR_UNSUPPORTED;
-  if (rays->num_rays == 0 || (!grad_origins_dev && !grad_directions_dev)) return RF_OK;
-  if (!has_caches(fwd)) return RF_ERR_NULL_POINTER;
-  if (!grid->features_dev && grid->num_features > 3) return RF_ERR_NULL_POINTER;
-  const GridArgs g = to_args(grid);
-  const RayArgs r = to_args(rays, flags);
-  const OutArgs o = to_args(fwd);
-  GradArgs gr = {};
-  set_grads(grads, &gr);
-  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
-  return dispatch_render(grid->num_features / 3, flags & RF_FLAG_RENDER_DIFFUSE, [&](auto k, auto d) {
-    hipLaunchKernelGGL((render_backward_rays_kernel<decltype(k)::value, decltype(d)::value>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, o, gr, flags,
-                       grad_origins_dev, grad_directions_dev);
-    return launch_status();
-  });
-}
-
-int rf_build_occupancy(const RFGrid* grid, float threshold, uint32_t* occupancy_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (!occupancy_dev) return RF_ERR_NULL_POINTER;
-  const GridArgs g = to_args(grid);
-  const long long ncell = (long long)(g.X + 1) * (g.Y + 1) * (g.Z + 1);
-  const long long nwords = (ncell + 31) / 32;
-  hipLaunchKernelGGL(build_occupancy_kernel, dim3(grid_1d(ncell, 256, 256LL * 32)), dim3(256), 0, (hipStream_t)stream, g,
-                     threshold, occupancy_dev, nwords);
-  return launch_status();
-}
-
-int rf_upsample_grid(const RFGrid* src, const RFGrid* dst, void* stream) {
-  int rc = check_grid(src);
-  if (rc != RF_OK) return rc;
-  rc = check_grid(dst);
-  if (rc != RF_OK) return rc;
-  if (src->num_features != dst->num_features) return RF_ERR_BAD_SHAPE;
-  if (src->densities_dev == dst->densities_dev || (dst->features_dev && src->features_dev == dst->features_dev)) return RF_ERR_BAD_SHAPE;
-  const GridArgs gs = to_args(src), gd = to_args(dst);
-  const long long total = (long long)gd.X * gd.Y * gd.Z * (gd.F + 1);
-  hipLaunchKernelGGL(upsample_grid_kernel, dim3(grid_1d(total, 256, 256LL * 64)), dim3(256), 0, (hipStream_t)stream, gs, gd,
-                     const_cast<float*>(dst->densities_dev), const_cast<float*>(dst->features_dev), total);
-  return launch_status();
-}
-
-int rf_tv_grad(const RFGrid* grid, float weight_density, float weight_features, float epsilon, float* grad_first_dev,
-               float* grad_second_dev, float* sums_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (!(epsilon > 0.0f) || !std::isfinite(epsilon)) return RF_ERR_BAD_SHAPE;
-  if (!(weight_density >= 0.0f) || !(weight_features >= 0.0f) || !std::isfinite(weight_density) || !std::isfinite(weight_features)) return RF_ERR_BAD_SHAPE;
-  if (weight_density == 0.0f && weight_features == 0.0f) return RF_OK;
-  // which gradient tensors the weights reach: split / bricked storage keeps the degree-0 coefficients beside the density
-  const bool split = grid->layout != RF_LAYOUT_REFERENCE;
-  const bool need_first = weight_density != 0.0f || split;
-  const bool need_second = weight_features != 0.0f && !(split && grid->num_features == 3);
-  if ((need_first && !grad_first_dev) || (need_second && !grad_second_dev)) return RF_ERR_NULL_POINTER;
-  // the gradient is added to tensors of its own, never to the parameters
-  if ((grad_first_dev && grad_first_dev == grid->densities_dev) || (grad_second_dev && grad_second_dev == grid->features_dev)) return RF_ERR_BAD_SHAPE;
-  const GridArgs g = to_args(grid);
-  const int K = g.F / 3, C = g.F + 1;
-  // one float4 of a node per lane where every node record is whole, aligned float4s
-  const uintptr_t ptrs = (uintptr_t)grid->densities_dev | (uintptr_t)grid->features_dev | (uintptr_t)grad_first_dev | (uintptr_t)grad_second_dev;
-  const bool quads = split && C % 4 == 0 && g.dstride % 4 == 0 && g.fstride % 4 == 0 && (ptrs & 15u) == 0;
-  const long long row = (long long)g.Z * (quads ? C / 4 : C);
-  const dim3 blocks((unsigned)((row + kWave - 1) / kWave), (unsigned)((g.Y + kTvRows - 1) / kTvRows), (unsigned)((g.X + kTvSlab - 1) / kTvSlab));
-  const dim3 threads(kWave, kTvRows);
-  // the weights of the two MEANS as per-element factors: w = lambda_D / N, lambda_F / (N F)
-  const double nodes = (double)g.X * g.Y * g.Z;
-  const float wd = (float)((double)weight_density / nodes), wf = (float)((double)weight_features / (nodes * g.F));
-  auto launch = [&](auto kernel) {
-    hipLaunchKernelGGL(kernel, blocks, threads, 0, (hipStream_t)stream, g, wd, wf, epsilon, grad_first_dev, grad_second_dev, sums_dev);
-    return launch_status();
-  };
-  if (quads)
-    return dispatch_sh(K, ShEven{}, [&](auto k) {
-      constexpr int KK = decltype(k)::value;
-      return sums_dev ? launch(tv_grad_kernel<KK, 4, true>) : launch(tv_grad_kernel<KK, 4, false>);
-    });
-  return dispatch_sh(K, ShAll{}, [&](auto k) {
-    constexpr int KK = decltype(k)::value;
-    return sums_dev ? launch(tv_grad_kernel<KK, 1, true>) : launch(tv_grad_kernel<KK, 1, false>);
-  });
-}
-
-int rf_node_max_weight(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float* max_weight_dev, void* stream) {
-  int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  rc = check_rays(rays);
-  if (rc != RF_OK) return rc;
-  if (!max_weight_dev) return RF_ERR_NULL_POINTER;
-  if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
-  if (rays->num_rays == 0) return RF_OK;
-  const GridArgs g = to_args(grid);
-  const RayArgs r = to_args(rays, flags);
-  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
-  hipLaunchKernelGGL((node_max_weight_kernel<RF_NMW_GUARD != 0, RF_NMW_DEDUPE != 0>), dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags,
-                     reinterpret_cast<unsigned int*>(max_weight_dev));
-  return launch_status();
-}
-
-int rf_distortion(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float scale, const float* grad_loss_dev, float* loss_dev,
-                  float* grad_first_dev, void* stream) {
-  int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  rc = check_rays(rays);
-  if (rc != RF_OK) return rc;
-  if (!std::isfinite(rays->near) || !std::isfinite(rays->far) || rays->far == rays->near || !std::isfinite(scale)) return RF_ERR_BAD_SHAPE;
-  if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
-  // the gradient is added to a tensor of its own, never to the parameters
-  if (grad_first_dev && grad_first_dev == grid->densities_dev) return RF_ERR_BAD_SHAPE;
-  const bool want_grad = grad_first_dev != nullptr && scale != 0.0f;
-  if ((!want_grad && !loss_dev) || rays->num_rays == 0) return RF_OK;
-  const GridArgs g = to_args(grid);
-  const RayArgs r = to_args(rays, flags);
-  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
-  if (want_grad)
-    hipLaunchKernelGGL(distortion_kernel<true>, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, scale, grad_loss_dev, loss_dev,
-                       grad_first_dev);
-  else
-    hipLaunchKernelGGL(distortion_kernel<false>, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, 0.0f, (const float*)nullptr, loss_dev,
-                       (float*)nullptr);
-  return launch_status();
-}
-
-int rf_render_geometry(const RFGrid* grid, const RFRayBatch* rays, uint32_t flags, float quantile, const RFGeometryOut* out, void* stream) {
-  int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  rc = check_rays(rays);
-  if (rc != RF_OK) return rc;
-  if (!out || (!out->normal_dev && !out->quantile_depth_dev && !out->acc_dev)) return RF_ERR_NULL_POINTER;
-  if (!(quantile > 0.0f && quantile < 1.0f)) return RF_ERR_BAD_SHAPE;  // (NaN fails the comparison too)
-  if ((flags & RF_FLAG_OCCUPANCY_SKIP) && !grid->occupancy_dev) return RF_ERR_NULL_POINTER;
-  if (rays->num_rays == 0) return RF_OK;
-  const GridArgs g = to_args(grid);
-  const RayArgs r = to_args(rays, flags);
-  const unsigned blocks = (unsigned)((rays->num_rays + kWavesPerBlock - 1) / kWavesPerBlock);
-  hipLaunchKernelGGL(render_geometry_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g, r, flags, quantile, out->normal_dev,
-                     out->quantile_depth_dev, out->acc_dev);
-  return launch_status();
-}
-
-int rf_prune_grid(const RFGrid* grid, const float* max_weight_dev, float threshold, int32_t dilate, float fill_density, float* densities_dev,
-                  uint8_t* keep_dev, int64_t* counts_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (!max_weight_dev || !densities_dev) return RF_ERR_NULL_POINTER;
-  if (dilate < 0 || dilate > 4) return RF_ERR_BAD_SHAPE;
-  if (!(threshold >= 0.0f) || !std::isfinite(threshold)) return RF_ERR_BAD_SHAPE;
-  if (fill_density != fill_density) return RF_ERR_BAD_SHAPE;
-  if (grid->density_mode == RF_DENSITY_ABS && fill_density != 0.0f) return RF_ERR_BAD_SHAPE;  // |D| has one empty value
-  const GridArgs g = to_args(grid);
-  const long long nodes = (long long)g.X * g.Y * g.Z;
-  hipLaunchKernelGGL(prune_grid_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, max_weight_dev, threshold,
-                     (int)dilate, fill_density, densities_dev, keep_dev, reinterpret_cast<unsigned long long*>(counts_dev), nodes);
-  return launch_status();
-}
-
-int rf_node_bounds(const RFGrid* grid, float threshold, int32_t* bounds_dev, int64_t* count_dev, void* stream) {
-  const int rc = check_grid(grid);
-  if (rc != RF_OK) return rc;
-  if (!bounds_dev) return RF_ERR_NULL_POINTER;
-  if (!(threshold >= 0.0f)) return RF_ERR_BAD_SHAPE;  // (NaN fails the comparison too)
-  const GridArgs g = to_args(grid);
-  const long long nodes = (long long)g.X * g.Y * g.Z;
-  hipLaunchKernelGGL(node_bounds_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, threshold, bounds_dev,
-                     reinterpret_cast<unsigned long long*>(count_dev), nodes);
-  return launch_status();
-}
-
-int rf_resample_grid(const RFGrid* src, const RFGrid* dst, const float* scale, const float* offset, float fill_density, void* stream) {
-  int rc = check_grid(src);
-  if (rc != RF_OK) return rc;
-  rc = check_grid(dst);
-  if (rc != RF_OK) return rc;
-  if (!scale || !offset) return RF_ERR_NULL_POINTER;
-  if (src->num_features != dst->num_features) return RF_ERR_BAD_SHAPE;
-  ResampleMap m;
-  for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(scale[a]) || !(scale[a] > 0.0f) || !std::isfinite(offset[a])) return RF_ERR_BAD_SHAPE;
-    m.scale[a] = scale[a];
-    m.offset[a] = offset[a];
-  }
-  if (fill_density != fill_density) return RF_ERR_BAD_SHAPE;
-  // the destination is written while the source is read: no tensor of one may be a tensor of the other
-  const float* s[2] = {src->densities_dev, src->features_dev};
-  const float* d[2] = {dst->densities_dev, dst->features_dev};
-  for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j)
-      if (s[i] && s[i] == d[j]) return RF_ERR_BAD_SHAPE;
-  const GridArgs gs = to_args(src), gd = to_args(dst);
-  const long long total = (long long)gd.X * gd.Y * gd.Z * (gd.F + 1);
-  hipLaunchKernelGGL(resample_grid_kernel, dim3(grid_1d(total, 256, 256LL * 64)), dim3(256), 0, (hipStream_t)stream, gs, gd, m, fill_density,
-                     const_cast<float*>(dst->densities_dev), const_cast<float*>(dst->features_dev), total);
-  return launch_status();
-}
-
-int rf_convert_grid(const RFGrid* src, const RFGrid* dst, void* stream) {
-  int rc = check_grid(src);
-  if (rc != RF_OK) return rc;
-  rc = check_grid(dst);
-  if (rc != RF_OK) return rc;
-  if (src->num_features != dst->num_features) return RF_ERR_BAD_SHAPE;
-  for (int a = 0; a < 3; ++a)
-    if (src->dims[a] != dst->dims[a]) return RF_ERR_BAD_SHAPE;
-  if (src->densities_dev == dst->densities_dev || (dst->features_dev && src->features_dev == dst->features_dev)) return RF_ERR_BAD_SHAPE;
-  const GridArgs gs = to_args(src), gd = to_args(dst);
-  const unsigned int nodes = (unsigned)gd.X * (unsigned)gd.Y * (unsigned)gd.Z;
-  const int K = gd.F / 3;
-  if (src->layout == RF_LAYOUT_REFERENCE && dst->layout == RF_LAYOUT_SPLIT && (K == 1 || K == 9) && dst->density_stride == 4 &&
-      (K == 1 || dst->feature_stride == gd.F - 3) && (((uintptr_t)dst->densities_dev | (uintptr_t)dst->features_dev) & 15u) == 0 &&
-      (unsigned long long)nodes * 7ull < (1ull << 32)) {
-    float4* base = reinterpret_cast<float4*>(const_cast<float*>(dst->densities_dev));
-    float4* rest = reinterpret_cast<float4*>(const_cast<float*>(dst->features_dev));
-    const unsigned blocks = grid_1d((long long)nodes * ((gd.F + 1) / 4), 256, 256LL * 64);
-    return dispatch_sh(K, ShEven{}, [&](auto k) {
-      hipLaunchKernelGGL((reference_to_split_kernel<decltype(k)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, gs.dens, gs.feat, gs.dstride, gs.fstride, base, rest, nodes);
-      return launch_status();
-    });
-  }
-  if (src->layout == RF_LAYOUT_SPLIT && dst->layout == RF_LAYOUT_REFERENCE && (K == 1 || K == 9) && src->density_stride == 4 &&
-      (K == 1 || src->feature_stride == gd.F - 3) && (((uintptr_t)src->densities_dev | (uintptr_t)src->features_dev) & 15u) == 0 &&
-      (unsigned long long)nodes * 7ull < (1ull << 32)) {
-    const float4* base = reinterpret_cast<const float4*>(src->densities_dev);
-    const float4* rest = reinterpret_cast<const float4*>(src->features_dev);
-    float* dd = const_cast<float*>(dst->densities_dev);
-    float* df = const_cast<float*>(dst->features_dev);
-    if (dst->density_stride == 1 && dst->feature_stride == gd.F && (nodes & 3u) == 0 && (((uintptr_t)dd | (uintptr_t)df) & 15u) == 0 &&
-        (unsigned long long)nodes * (unsigned long long)gd.F < (1ull << 32)) {  // contiguous reference tensors: 16-byte stores
-      const unsigned blocks4 = grid_1d((long long)nodes * gd.F / 4 + nodes / 4, 256, 256LL * 64);
-      return dispatch_sh(K, ShEven{}, [&](auto k) {
-        hipLaunchKernelGGL((split_to_reference_quads_kernel<decltype(k)::value>), dim3(blocks4), dim3(256), 0, (hipStream_t)stream, src->densities_dev, src->features_dev,
-                           reinterpret_cast<float4*>(dd), reinterpret_cast<float4*>(df), nodes);
-        return launch_status();
-      });
-    }
-    const unsigned blocks = grid_1d((long long)nodes * ((gd.F + 1) / 4), 256, 256LL * 64);
-    return dispatch_sh(K, ShEven{}, [&](auto k) {
-      hipLaunchKernelGGL((split_to_reference_kernel<decltype(k)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, base, rest, dd, df, gd.dstride, gd.fstride, nodes);
-      return launch_status();
-    });
-  }
-  const int cw = gd.F + 1 <= 32 ? 32 : 64, per_block = 256 / cw;
-  hipLaunchKernelGGL(convert_grid_kernel, dim3(grid_1d(nodes, per_block, 256LL * 256)), dim3(cw, per_block), 0, (hipStream_t)stream, gs, gd,
-                     const_cast<float*>(dst->densities_dev), const_cast<float*>(dst->features_dev), nodes);
-  return launch_status();
 }
 
 static int l1_loss_grad_impl(const L1Sets& sets, int nsets, const float* target_dev, int64_t num_rays, float scale, void* stream) {

@@ -5,7 +5,8 @@ thre3d_atom/thre3d_reprs/voxels.py (VoxelGrid :46-331, scale_voxel_grid_with_req
 Same constructor arguments, properties, state_dict keys (``_densities`` / ``_features``) and config
 dictionaries as the reference, so trainers and checkpoints written against it keep working.  The
 arithmetic itself (normalise -> trilinear gather -> ReLU) lives in the HIP kernels
-(csrc/relu_field_kernels.hip); this class only owns the tensors and describes them to the C ABI.
+(csrc/relu_field_kernels.hip for the renders, csrc/grid_kernels.hip for point queries, scaling, re-layout and pruning); this class
+only owns the tensors and describes them to the C ABI.
 """
 from typing import Any, Callable, Dict, NamedTuple, Optional, Tuple
 

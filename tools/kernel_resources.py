@@ -1,14 +1,19 @@
 #!/usr/bin/env python
-"""Per-kernel register / LDS / occupancy summary of a HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_resources.py [file.hip] [include dir] [substring filter ...]"""
+"""Per-kernel register / LDS / occupancy summary of HIP sources (hipcc -Rpass-analysis=kernel-resource-usage).
+usage: python tools/kernel_resources.py [file.hip] [include dir] [substring filter ...]
+Without a file (or with "-" in its place) every unit of thr3ed_atom_amd/_lib.py:SOURCES is covered."""
+import os
 import re
 import subprocess
 import sys
 
-src = sys.argv[1] if len(sys.argv) > 1 else "thr3ed_atom_amd/csrc/relu_field_kernels.hip"
-inc = sys.argv[2] if len(sys.argv) > 2 else "include"
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from thr3ed_atom_amd import _lib  # noqa: E402  (ctypes only: nothing is loaded)
+
+srcs = [sys.argv[1]] if len(sys.argv) > 1 and sys.argv[1] != "-" else [os.path.join(_lib.CSRC_DIR, s) for s in _lib.SOURCES]
+inc = sys.argv[2] if len(sys.argv) > 2 else _lib.INCLUDE_DIR
 filters = sys.argv[3:]
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", inc, src, "-o", "/tmp/kr.so",
+cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-I", inc, *srcs, "-o", "/tmp/kr.so",
        "-Rpass-analysis=kernel-resource-usage"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, {}
