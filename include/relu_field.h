@@ -595,6 +595,32 @@ int rf_ssim_forward(const RFImage* image, const RFImage* target, int32_t height,
 int rf_ssim_backward(const RFImage* image, const RFImage* target, int32_t height, int32_t width, int32_t channels, int32_t padding,
                      const float* dmaps_dev, const float* grad_mean_dev, const RFImage* grad_image, void* stream);
 
+/* ---- vector quantisation (csrc/vq_kernels.hip) ---------------------------------------------------------------------------
+ * The two halves of an importance-weighted Lloyd iteration over feature vectors: what compresses a trained field (VQRF, Li et al.
+ * 2023; thr3ed_atom_amd/compression.py).  Sizes: 1 <= dim <= 64, 1 <= num_codes <= 65536.
+ *
+ * rf_vq_assign: for every row x of vectors_dev [num_vectors, dim] (float32, rows row_stride >= dim floats apart) the index of the
+ *   nearest row of codebook_dev [num_codes, dim] (float32, contiguous) by squared Euclidean distance -> index_out_dev [num_vectors],
+ *   and that distance -> dist_out_dev [num_vectors].  Codes are RANKED by s = ||c||^2 - 2 x.c, one k-ordered float32 fma chain per
+ *   pair on the exact-f32 MFMA starting from ||c||^2 (float64 sum, rounded once): every ranked value is within
+ *   (dim + 1) u (||c||^2 + 2 sum_k |x_k c_k|), u = 2^-24, of the true one.  Among computed-equal values the LOWEST index wins; the
+ *   same inputs give the same bits; the distances are never stored and there are no atomics.  dist_out is not the ranked value: it
+ *   is sum_k (x_k - c_jk)^2 of the winner j recomputed in ascending k in float32 without contraction -- within (dim + 2) u,
+ *   relative, of the true distance to the returned code.  num_vectors == 0 is a no-op that returns RF_OK.
+ * rf_vq_centroids: the weighted Lloyd update in gather form.  order_dev [num_vectors] (int32) lists the vector indices sorted by
+ *   assigned code, offsets_dev [num_codes + 1] (int64) bounds the segment of every code in it.  A code with a non-empty segment and a
+ *   positive weight sum gets codebook_inout_dev[c] = sum w x / sum w over its segment; any other code keeps its bits.
+ *   weight_sum_out_dev [num_codes] (optional, NULL: not written) receives every code's weight sum (0 for an empty segment).  The order
+ *   of every sum is fixed by the segment alone (16 interleaved sequential streams, then a fixed tree): no atomics, reproducible bits.
+ *   The entries of order_dev must be valid row indices: the caller answers for that.
+ * Before any launch: RF_ERR_NULL_POINTER (any array but the optional one; rf_vq_assign with num_vectors == 0 needs the codebook
+ * only), RF_ERR_UNSUPPORTED (dim or num_codes out of range), RF_ERR_BAD_SHAPE (num_vectors < 0, row_stride < dim, more than 2^31 - 1
+ * workgroups, an output that is another argument's array).  (Added to ABI version 4 compatibly: no struct or signature changed.) */
+int rf_vq_assign(const float* vectors_dev, int64_t num_vectors, int32_t dim, int64_t row_stride, const float* codebook_dev, int32_t num_codes,
+                 int32_t* index_out_dev, float* dist_out_dev, void* stream);
+int rf_vq_centroids(const float* vectors_dev, int64_t row_stride, int32_t dim, const float* weights_dev, const int32_t* order_dev,
+                    const int64_t* offsets_dev, int32_t num_codes, float* codebook_inout_dev, float* weight_sum_out_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

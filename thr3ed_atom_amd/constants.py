@@ -32,6 +32,7 @@ RENDER_CONFIG = "render_config"
 RENDER_CONFIG_TYPE = "render_config_type"
 STATE_DICT = "state_dict"
 CONFIG_DICT = "config_dict"
+COMPRESSED_STATE = "compressed_state"  # in place of STATE_DICT in a compact checkpoint: the bytes of CompressedField.to_bytes() as a uint8 tensor (an extension of this build)
 EXTRA_INFO = "extra_info"
 u_DENSITIES = "_densities"
 u_FEATURES = "_features"

@@ -12,6 +12,7 @@ from torch.nn import Module
 
 from .camera import CameraIntrinsics, CameraPose
 from .constants import (
+    COMPRESSED_STATE,
     CONFIG_DICT,
     EXTRA_INFO,
     RENDER_CONFIG,
@@ -79,10 +80,20 @@ class VolumetricModel:
             setattr(updated, field, value)
         return updated
 
-    def get_save_info(self, extra_info: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    def get_save_info(self, extra_info: Optional[Dict[str, Any]] = None, compressed=None) -> Dict[str, Any]:
+        """The checkpoint dictionary (reference :83-97).  ``compressed`` (a ``CompressedField`` of this model's grid; an extension
+        of this build): the ``thre3d_repr`` entry carries its bytes as ``compressed_state`` in place of the state dict --
+        ``create_voxel_grid_from_saved_info_dict`` decompresses them, so every loader of checkpoints reads the compact file.  The
+        bytes travel as a uint8 tensor: ``torch.save`` writes a tensor's storage verbatim, while a ``bytes`` object goes through
+        pickle protocol 2's latin-1 detour and grows by half."""
+        if compressed is not None:
+            grid_dims = tuple(int(v) for v in getattr(self._thre3d_repr, "grid_dims", compressed.dims))
+            if tuple(compressed.dims) != grid_dims:
+                raise ValueError(f"the compressed field is {tuple(compressed.dims)}, the model's grid {grid_dims}")
+        state = {STATE_DICT: self._thre3d_repr.state_dict()} if compressed is None else {COMPRESSED_STATE: torch.frombuffer(bytearray(compressed.to_bytes()), dtype=torch.uint8)}
         info = {
             THRE3D_REPR: {
-                STATE_DICT: self._thre3d_repr.state_dict(),
+                **state,
                 CONFIG_DICT: self._thre3d_repr.get_save_config_dict(),
             },
             RENDER_PROCEDURE: self._render_procedure,

@@ -20,7 +20,7 @@ from torch.nn import Module
 
 from . import _lib
 from .camera import slack_range_map
-from .constants import CONFIG_DICT, STATE_DICT, THRE3D_REPR, u_DENSITIES, u_FEATURES
+from .constants import COMPRESSED_STATE, CONFIG_DICT, STATE_DICT, THRE3D_REPR, u_DENSITIES, u_FEATURES
 
 
 class VoxelSize(NamedTuple):
@@ -725,7 +725,16 @@ def scale_voxel_grid_with_required_output_size(
 
 
 def create_voxel_grid_from_saved_info_dict(saved_info: Dict[str, Any], storage: str = "reference") -> VoxelGrid:
-    """Rebuild a grid from the ``thre3d_repr`` entry of a checkpoint (reference voxels.py:376-383)."""
+    """Rebuild a grid from the ``thre3d_repr`` entry of a checkpoint (reference voxels.py:376-383).  A compact checkpoint
+    (``VolumetricModel.get_save_info(compressed=...)``) carries a ``compressed_state`` entry in place of the state dict: it is
+    decompressed into a dense grid."""
+    if COMPRESSED_STATE in saved_info[THRE3D_REPR]:
+        from .compression import CompressedField
+
+        entry = saved_info[THRE3D_REPR]
+        payload = entry[COMPRESSED_STATE]  # a uint8 tensor (what get_save_info writes) or plain bytes
+        payload = payload.cpu().numpy().tobytes() if isinstance(payload, Tensor) else bytes(payload)
+        return CompressedField.from_bytes(payload, config=entry[CONFIG_DICT]).decompress(storage=storage)
     state = saved_info[THRE3D_REPR][STATE_DICT]
     grid = VoxelGrid(
         densities=torch.empty_like(state[u_DENSITIES]),
