@@ -621,6 +621,24 @@ int rf_vq_assign(const float* vectors_dev, int64_t num_vectors, int32_t dim, int
 int rf_vq_centroids(const float* vectors_dev, int64_t row_stride, int32_t dim, const float* weights_dev, const int32_t* order_dev,
                     const int64_t* offsets_dev, int32_t num_codes, float* codebook_inout_dev, float* weight_sum_out_dev, void* stream);
 
+/* ---- connected components (csrc/component_kernels.hip) ---------------------------------------------------------------------
+ * Labels the connected components of the OCCUPIED nodes of a field: what floater removal is built on
+ * (thr3ed_atom_amd/components.py).  Node n is occupied iff its own activated density
+ * sigma_n = post(pre(D_n * density_scale)) > threshold -- the predicate of rf_node_bounds bit for bit (strict; |.| on the
+ * pre-activation under RF_DENSITY_ABS; no interpolation; only the node's density element is read, never a padding node of bricked
+ * storage).  connectivity 6 / 18 / 26: face, face + edge, face + edge + corner neighbours on the node lattice.
+ *   labels_dev [X, Y, Z] (int32, plain node order whatever the layout): -1 for an unoccupied node, otherwise the SMALLEST plain
+ *     linear index (x * Y + y) * Z + z of any node of the same component.  Canonical: independent of launch order, storage and run;
+ *     two calls give identical bits.  Every element is written.
+ *   sizes_dev [X * Y * Z] (int32, optional): sizes[r] = the number of nodes of the component labelled r, 0 everywhere else.  Every
+ *     element is written (no pre-zeroing).
+ * Three launches on `stream` (per-tile labelling in LDS, a lock-free union of the tiles' trees with integer atomicMin, flatten +
+ * count), no host synchronisation, no scratch beyond the two outputs; no kernel waits for another workgroup.  Before any device
+ * access: RF_ERR_NULL_POINTER (grid, its tensors, labels_dev), RF_ERR_BAD_SHAPE (dims, a NaN or negative threshold, a connectivity
+ * other than 6 / 18 / 26, more than 2^31 - 1 nodes, sizes_dev == labels_dev).  (Added to ABI version 4 compatibly: no existing
+ * struct or signature changed.) */
+int rf_label_components(const RFGrid* grid, float threshold, int32_t connectivity, int32_t* labels_dev, int32_t* sizes_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

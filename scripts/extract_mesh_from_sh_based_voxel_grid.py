@@ -4,6 +4,11 @@ of the ReLU field sampled at sub-voxel resolution on the GPU (thr3ed_atom_amd.me
 reference load (create_volumetric_model_from_saved_model maps the reference's pickled names).
 
     python scripts/extract_mesh_from_sh_based_voxel_grid.py -i out/saved_models/model_final.pth -o mesh.ply --subdivisions 2
+    python scripts/extract_mesh_from_sh_based_voxel_grid.py -i model.pth -o mesh.ply --keep_largest 1
+
+--keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
+whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
+not touched.
 """
 import math
 import os
@@ -26,9 +31,15 @@ import thr3ed_atom_amd as rf  # noqa: E402
 @click.option("--iso_level", type=click.FLOAT, default=None, required=False,
               help="density of the surface; default ln 2 / min(voxel_size): a one-voxel slab at that density is 50 % opaque")
 @click.option("--subdivisions", type=click.IntRange(min=1, max=8), default=2, required=False, help="lattice points per voxel and axis (sub-voxel surfaces of the ReLU field)")
+@click.option("--keep_largest", type=click.IntRange(min=1), default=None, required=False, help="keep only this many of the largest connected components of the nodes above the iso level")
+@click.option("--min_component_nodes", type=click.IntRange(min=1), default=None, required=False, help="drop the connected components with fewer nodes above the iso level than this")
+@click.option("--fill_density", type=click.FLOAT, default=None, required=False, help="raw density of an emptied node (default 0; required for softplus fields, e.g. -10)")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
+    filtering = config["keep_largest"] is not None or config["min_component_nodes"] is not None
+    if filtering and config["iso_level"] is not None and config["iso_level"] < 0.0:
+        raise click.UsageError("--keep_largest / --min_component_nodes need a non-negative --iso_level (the occupancy threshold of the components)")
     dev = torch.device("cuda:0")
     creator = lambda info: rf.create_voxel_grid_from_saved_info_dict(info, storage="split")  # noqa: E731
     model, _ = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)
@@ -36,6 +47,9 @@ def main(**kwargs) -> None:
     iso = config["iso_level"]
     if iso is None:
         iso = math.log(2.0) / min(grid._voxel_size)
+    if filtering:
+        stats = rf.remove_small_components(grid, iso, 26, min_nodes=config["min_component_nodes"], keep_largest=config["keep_largest"], fill_density=config["fill_density"])
+        print(f"connected components above the iso level: {stats.components}, removed {stats.removed_components} ({stats.removed_nodes} nodes; {stats.kept_nodes} kept)")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     mesh = rf.extract_mesh(grid, iso, subdivisions=config["subdivisions"])

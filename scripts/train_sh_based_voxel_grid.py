@@ -118,6 +118,12 @@ def load_datasets(config, dev):
 @click.option("--tighten_threshold", type=click.FLOAT, required=False, default=-1.0,
               help="at the end of every stage but the last, tighten the box to the nodes whose activated density exceeds this and spend the next stage's nodes inside it (negative: off)")
 @click.option("--tighten_margin", type=click.IntRange(min=0), required=False, default=1, help="nodes kept around the content box when tightening")
+@click.option("--component_keep_largest", type=click.IntRange(min=1), required=False, default=None,
+              help="at the end of every stage, keep only this many of the largest connected components of the occupied nodes and empty the rest (default: off)")
+@click.option("--component_min_nodes", type=click.IntRange(min=1), required=False, default=None,
+              help="at the end of every stage, empty the connected components with fewer nodes of the stage's grid than this (default: off)")
+@click.option("--component_threshold", type=click.FloatRange(min=0.0), required=False, default=0.0, help="a node is occupied when its own activated density exceeds this")
+@click.option("--component_connectivity", type=click.Choice(["6", "18", "26"]), required=False, default="26", help="neighbours of a node: faces, + edges, + corners")
 @click.option("--report_ssim", type=click.BOOL, required=False, default=False, help="the periodic test also reports the held-out SSIM (test_ssim)")
 @click.option("--seed", type=click.INT, required=False, default=42, help="seed of torch's generators")
 # fmt: on
@@ -163,6 +169,8 @@ def main(**kwargs) -> None:
         tv_epsilon=config["tv_epsilon"], distortion_weight=config["distortion_weight"], prune_threshold=config["prune_threshold"] if config["prune_threshold"] >= 0.0 else None,
         prune_dilate=config["prune_dilate"], tighten_threshold=config["tighten_threshold"] if config["tighten_threshold"] >= 0.0 else None,
         tighten_margin=config["tighten_margin"], report_ssim=config["report_ssim"],
+        component_keep_largest=config["component_keep_largest"], component_min_nodes=config["component_min_nodes"],
+        component_threshold=config["component_threshold"], component_connectivity=int(config["component_connectivity"]),
     )
 
 

@@ -53,6 +53,7 @@ from .geometry import back_project_points, normal_map_image, write_point_cloud_p
 from .pose_refinement import pose_error, refine_camera_pose  # noqa: F401
 from .pruning import PruneStats, node_max_weights, prune_voxel_grid  # noqa: F401
 from .resampling import TightenStats, content_bounds, crop_voxel_grid, resample_voxel_grid, tighten_voxel_grid  # noqa: F401
+from .components import ComponentStats, Components, label_components, remove_small_components  # noqa: F401
 from .compression import CompressedField, compress_voxel_grid, partition_by_shares, vq_assign, vq_kmeans, vq_update_centroids  # noqa: F401
 
 __version__ = "0.1.0"

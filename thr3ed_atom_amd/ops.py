@@ -1385,6 +1385,25 @@ def node_bounds_raw(grid: VoxelGrid, threshold: float, bounds: Tensor, count: Op
     _lib.check(rc, "rf_node_bounds")
 
 
+def label_components_raw(grid: VoxelGrid, threshold: float, connectivity: int, labels: Tensor, sizes: Optional[Tensor] = None) -> None:
+    """Enqueue rf_label_components (include/relu_field.h): ``labels`` (int32 [X, Y, Z], plain node order) receives -1 for a node whose
+    own activated density does not exceed ``threshold`` and otherwise the smallest plain linear index of its connected component
+    (``connectivity`` 6, 18 or 26); ``sizes`` (optional int32 [X * Y * Z]) receives the component sizes at the label positions and 0
+    elsewhere.  Both are overwritten entirely.  Three launches, no host synchronisation.  No autograd."""
+    lib = _lib.load()
+    _check_node_buffer(grid, labels, torch.int32, "labels")
+    if sizes is not None:
+        _require_hip(sizes, "sizes")
+        if sizes.dtype != torch.int32 or sizes.numel() != labels.numel() or not sizes.is_contiguous():
+            raise ValueError(f"sizes must be a contiguous int32 tensor of {labels.numel()} elements")
+    first, _ = grid.kernel_tensors()
+    _require_hip(first, "grid tensor")
+    rf_grid = grid.to_rf_grid()  # (only a node's density element is read: no shadow needed)
+    with _span("label_components", first.device):
+        rc = lib.rf_label_components(C.byref(rf_grid), float(threshold), int(connectivity), labels.data_ptr(), _ptr(sizes), _stream(first.device))
+    _lib.check(rc, "rf_label_components")
+
+
 def resample_grid_raw(src: VoxelGrid, dst: VoxelGrid, scale, offset, fill_density: float = 0.0) -> None:
     """Enqueue rf_resample_grid (include/relu_field.h): overwrite the tensors of ``dst`` with the raw channels of ``src`` at the
     continuous source indices ``s_a = fma(scale_a, i_a, offset_a)`` of its nodes (trilinear; ``(fill_density, 0 ...)`` outside the

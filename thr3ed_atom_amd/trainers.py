@@ -1196,6 +1196,10 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     tighten_threshold: Optional[float] = None,
     tighten_margin: int = 1,
     report_ssim: bool = False,
+    component_keep_largest: Optional[int] = None,
+    component_min_nodes: Optional[int] = None,
+    component_threshold: float = 0.0,
+    component_connectivity: int = 26,
 ) -> VolumetricModel:
     """Same arguments (minus the feedback/visualisation ones) and same schedule as the reference's
     trainer.  Returns the trained model; ``history`` (if given) collects the logged scalars.
@@ -1219,7 +1223,15 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
     old and new dims and boxes.  A field without such a node is up-scaled as usual.  Replicas of a process group hold identical
     parameters, so every rank computes the same box: no communication.
     ``report_ssim``: the periodic test also reports the mean SSIM of the held-out views (metrics.ssim, "valid" windows) as
-    ``test_ssim`` in its ``history`` row and in the log line; off, nothing new is computed, allocated or written."""
+    ``test_ssim`` in its ``history`` row and in the log line; off, nothing new is computed, allocated or written.
+    ``component_keep_largest`` / ``component_min_nodes`` (both None = off: nothing is launched or allocated) /
+    ``component_threshold`` / ``component_connectivity``: at the end of every stage -- after the optional pruning, before the
+    tightening / up-scale, and once after the last stage -- the connected components of the nodes whose own activated density
+    exceeds the threshold are labelled and those that are too small or rank too low are emptied
+    (components.remove_small_components); ``history`` gets a row with the counts.  ``component_min_nodes`` counts nodes of the
+    CURRENT stage's grid: the same piece of the scene holds about ``scale_factor``^3 times as many nodes one stage later.  Replicas
+    of a process group hold bit-identical parameters and the labelling is a deterministic function of them, so every rank removes
+    the same nodes: no communication."""
     grid = vol_mod.thre3d_repr
     assert isinstance(grid, VoxelGrid), f"cannot use a {type(grid)} with this TrainProcedure"
     assert vol_mod.render_procedure is render_sh_voxel_grid, "non SH-based VoxelGrids cannot be used with this TrainProcedure"
@@ -1321,6 +1333,17 @@ def train_sh_vox_grid_vol_mod_with_posed_images(
                 history.append(row)
             if is_main:
                 log(f"pruned {pruned.pruned} of {pruned.pruned + pruned.kept} nodes after stage {stage} (threshold {prune_threshold}, dilate {prune_dilate})")
+        if component_keep_largest is not None or component_min_nodes is not None:
+            from .components import remove_small_components
+
+            cleaned = remove_small_components(vol_mod.thre3d_repr, component_threshold, component_connectivity, min_nodes=component_min_nodes,
+                                              keep_largest=component_keep_largest)
+            row = {"stage": stage, "components": cleaned.components, "removed_components": cleaned.removed_components, "removed_nodes": cleaned.removed_nodes}
+            if history is not None:
+                history.append(row)
+            if is_main:
+                log(f"removed {cleaned.removed_components} of {cleaned.components} connected components ({cleaned.removed_nodes} nodes, {cleaned.kept_nodes} kept) after stage {stage} "
+                    f"(threshold {component_threshold}, connectivity {component_connectivity}, keep_largest {component_keep_largest}, min_nodes {component_min_nodes})")
         if stage != num_stages:
             tightened = None
             if tighten_threshold is not None:
