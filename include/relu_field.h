@@ -639,6 +639,38 @@ int rf_vq_centroids(const float* vectors_dev, int64_t row_stride, int32_t dim, c
  * struct or signature changed.) */
 int rf_label_components(const RFGrid* grid, float threshold, int32_t connectivity, int32_t* labels_dev, int32_t* sizes_dev, void* stream);
 
+/* ---- mesh simplification by vertex clustering with quadric-error representatives (csrc/mesh_simplify_kernels.hip; DESIGN.md
+ * section 20; thr3ed_atom_amd/mesh_simplify.py sorts, builds the lists and rewrites the faces between the two calls) ----------
+ * A uniform lattice of cubic cells of edge h = cell size starts at `origin` (HOST float[3]); `cells` (HOST int32[3]) is the number
+ * n_a of cells per axis, each in [1, 2^20].  Any indexed triangle mesh: vertices_dev [V, 3] float32, faces_dev [T, 3] int64.
+ * rf_mesh_cluster_keys: keys_dev[v] = (k_x n_y + k_y) n_z + k_z with k_a = floor(fl32(fl32(v_a - origin_a) * r)), r = fl32(1 / h)
+ *   computed by the caller (two rounded float32 operations: the library is built without contraction).  A vertex with a k_a outside
+ *   [0, n_a) -- below the origin, beyond the cells, NaN, infinite -- gets the key -1 and sets status_dev[0] (int32, zeroed by the
+ *   caller) to 1 in the same pass.  One pointwise launch.
+ * rf_mesh_cluster_vertices: the representative of every cluster, ONE launch, gather form, no atomics, float64 accumulators, every
+ *   sum in an order fixed by the lists alone (two calls give identical bits).  cluster_keys_dev [C] are the distinct keys, ascending;
+ *   members_dev [V] the vertex indices stably sorted by cluster and corners_dev [3 T] the corner ids 3 f + j stably sorted by the
+ *   cluster of vertex faces[f][j], with member_begin_dev / corner_begin_dev [C + 1] bounding the segment of every cluster (all
+ *   int64).  In coordinates local to the centre m of the cluster's cell, q = p - m in float64: every corner record adds its face's
+ *   n = (q1 - q0) x (q2 - q0), d = n . q0 as A += n n^T, b += d n; xbar = the mean of the members.  placement
+ *   RF_MESH_PLACEMENT_MEAN, or tr A == 0: x = xbar.  RF_MESH_PLACEMENT_QUADRIC: x = xbar + (A + regularisation tr(A) I)^-1
+ *   (b - A xbar), clamped per axis to [-h/2, h/2].  vertices_out_dev [C, 3] = float32(m + x); colours_out_dev [C, 3] = the mean of the
+ *   members' colours; normals_out_dev [C, 3] = the members' normal sum over its norm ((0,0,0) where the sum is 0).  colours / normals
+ *   are optional: input and output are both given or both NULL.  Indices read from the lists are checked against their arrays.
+ * Before any launch, in this order: RF_ERR_NULL_POINTER (any array but the optional pairs; an optional pair given by halves), then
+ * RF_ERR_BAD_SHAPE for negative counts, num_vertices >= 2^31 (num_clusters > num_vertices, num_faces >= 2^40), h or r (or 1 / h) not
+ * finite or <= 0, a non-finite origin, a cell count outside [1, 2^20], a placement other than the two, a regularisation outside
+ * [1e-6, 1]; then zero vertices / zero clusters return RF_OK without a launch.  (Added to ABI version 4 compatibly: no existing
+ * struct or signature changed.) */
+enum { RF_MESH_PLACEMENT_QUADRIC = 0, RF_MESH_PLACEMENT_MEAN = 1 };
+int rf_mesh_cluster_keys(const float* vertices_dev, int64_t num_vertices, const float* origin, float r, const int32_t* cells, int64_t* keys_dev,
+                         int32_t* status_dev, void* stream);
+int rf_mesh_cluster_vertices(const float* vertices_dev, const float* colours_dev, const float* normals_dev, int64_t num_vertices,
+                             const int64_t* faces_dev, int64_t num_faces, const int64_t* members_dev, const int64_t* member_begin_dev,
+                             const int64_t* corners_dev, const int64_t* corner_begin_dev, const int64_t* cluster_keys_dev, int64_t num_clusters,
+                             const float* origin, float h, const int32_t* cells, int32_t placement, float regularisation,
+                             float* vertices_out_dev, float* colours_out_dev, float* normals_out_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

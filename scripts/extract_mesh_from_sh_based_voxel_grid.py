@@ -6,6 +6,13 @@ reference load (create_volumetric_model_from_saved_model maps the reference's pi
     python scripts/extract_mesh_from_sh_based_voxel_grid.py -i out/saved_models/model_final.pth -o mesh.ply --subdivisions 2
     python scripts/extract_mesh_from_sh_based_voxel_grid.py -i model.pth -o mesh.ply --keep_largest 1
 
+    python scripts/extract_mesh_from_sh_based_voxel_grid.py -i model.pth -o mesh.ply --simplify_voxels 2
+    python scripts/extract_mesh_from_sh_based_voxel_grid.py -i model.pth -o mesh.ply --target_faces 200000
+
+--simplify_voxels X / --target_faces N simplify the mesh on the GPU before it is written (thr3ed_atom_amd.mesh_simplify: vertex
+clustering with quadric-error representatives): cells of X * min(voxel_size) that start at the grid's AABB minimum, so the clusters
+align with the voxels, or the finest cells that leave at most N faces.  Off by default.
+
 --keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
 whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
 not touched.
@@ -16,6 +23,7 @@ import sys
 import time
 
 import click
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,9 +42,15 @@ import thr3ed_atom_amd as rf  # noqa: E402
 @click.option("--keep_largest", type=click.IntRange(min=1), default=None, required=False, help="keep only this many of the largest connected components of the nodes above the iso level")
 @click.option("--min_component_nodes", type=click.IntRange(min=1), default=None, required=False, help="drop the connected components with fewer nodes above the iso level than this")
 @click.option("--fill_density", type=click.FLOAT, default=None, required=False, help="raw density of an emptied node (default 0; required for softplus fields, e.g. -10)")
+@click.option("--simplify_voxels", type=click.FloatRange(min=0.0, min_open=True), default=None, required=False,
+              help="simplify the mesh by vertex clustering with cells of this many (smallest) voxel edges, aligned with the grid")
+@click.option("--target_faces", type=click.IntRange(min=0), default=None, required=False, help="simplify the mesh to at most this many faces")
+@click.option("--simplify_placement", type=click.Choice(["quadric", "mean"]), default="quadric", required=False, help="where a cluster's vertex goes")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
+    if config["simplify_voxels"] is not None and config["target_faces"] is not None:
+        raise click.UsageError("--simplify_voxels and --target_faces exclude each other")
     filtering = config["keep_largest"] is not None or config["min_component_nodes"] is not None
     if filtering and config["iso_level"] is not None and config["iso_level"] < 0.0:
         raise click.UsageError("--keep_largest / --min_component_nodes need a non-negative --iso_level (the occupancy threshold of the components)")
@@ -55,10 +69,28 @@ def main(**kwargs) -> None:
     mesh = rf.extract_mesh(grid, iso, subdivisions=config["subdivisions"])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    extracted, summary = (len(mesh.vertices), len(mesh.faces)), ""
+    if (config["simplify_voxels"] is not None or config["target_faces"] is not None) and len(mesh.faces):
+        t1 = time.perf_counter()
+        if config["target_faces"] is not None:
+            mesh, stats = rf.simplify_mesh(mesh, target_faces=config["target_faces"], placement=config["simplify_placement"], return_stats=True)
+        else:
+            # cells aligned with the voxels: the origin is the AABB minimum, moved down by whole cells where the surface's guard
+            # layer reaches below it
+            h = np.float32(config["simplify_voxels"] * min(grid.voxel_size))
+            origin = np.asarray([r[0] for r in grid.aabb], dtype=np.float32)
+            lowest = mesh.vertices.amin(dim=0).cpu().numpy()
+            origin = origin - np.ceil(np.maximum(origin - lowest, 0.0) / h).astype(np.float32) * h
+            origin = np.where(origin > lowest, origin - h, origin).astype(np.float32)  # (float32 rounding of the step)
+            mesh, stats = rf.simplify_mesh(mesh, float(h), origin=origin.tolist(), placement=config["simplify_placement"], return_stats=True)
+        torch.cuda.synchronize()
+        summary = (f"simplified ({config['simplify_placement']}, cell size {stats.cell_size:.6g}): V = {extracted[0]} -> {len(mesh.vertices)}, "
+                   f"T = {extracted[1]} -> {len(mesh.faces)} in {1e3 * (time.perf_counter() - t1):.1f} ms\n")
     out_dir = os.path.dirname(os.path.abspath(config["output_path"]))
     os.makedirs(out_dir, exist_ok=True)
     rf.write_ply(mesh, config["output_path"])
-    print(f"grid {grid.grid_dims}, iso_level {iso:.6g}, subdivisions {config['subdivisions']}: V = {len(mesh.vertices)}, T = {len(mesh.faces)} "
+    print(summary, end="")
+    print(f"grid {grid.grid_dims}, iso_level {iso:.6g}, subdivisions {config['subdivisions']}: V = {extracted[0]}, T = {extracted[1]} "
           f"in {1e3 * dt:.1f} ms (extraction incl. host synchronisation) -> {config['output_path']}")
 
 

@@ -1,0 +1,56 @@
+#!/usr/bin/env python
+"""Simplify a triangle mesh (a binary PLY as ``write_ply`` and scripts/extract_mesh_from_sh_based_voxel_grid.py write it) on the GPU
+by vertex clustering with quadric-error representatives (thr3ed_atom_amd.mesh_simplify).
+
+    python scripts/simplify_mesh.py -i mesh.ply -o small.ply --cell_size 0.02
+    python scripts/simplify_mesh.py -i mesh.ply -o small.ply --target_faces 100000 --placement mean
+
+The PLY's uint8 colours are read as colour / 255 and its normals as they are: all-zero normals and all-255 colours -- what write_ply
+stores for a mesh without them -- pass through as data.  Opposed face pairs of collapsed thin sheets are kept; this is vertex
+clustering, not edge collapse.
+"""
+import os
+import sys
+import time
+
+import click
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import thr3ed_atom_amd as rf  # noqa: E402
+from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
+
+
+# fmt: off
+@click.command()
+@click.option("-i", "--input_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="the .ply file to read")
+@click.option("-o", "--output_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="the .ply file to write")
+@click.option("--cell_size", type=click.FLOAT, default=None, required=False, help="edge of the cubic clustering cells, in the mesh's units")
+@click.option("--target_faces", type=click.IntRange(min=0), default=None, required=False, help="the finest cells that leave at most this many faces")
+@click.option("--placement", type=click.Choice(["quadric", "mean"]), default="quadric", required=False, help="where a cluster's vertex goes")
+@click.option("--regularisation", type=click.FloatRange(min=1e-6, max=1.0), default=1e-3, required=False, help="pull of the quadric minimiser towards the cluster's mean vertex")
+# fmt: on
+def main(**kwargs) -> None:
+    config = dict(kwargs)
+    if (config["cell_size"] is None) == (config["target_faces"] is None):
+        raise click.UsageError("give --cell_size or --target_faces (one of the two)")
+    dev = torch.device("cuda:0")
+    vertices, normals, colours, faces = read_ply(config["input_path"])
+    on_device = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    mesh = rf.Mesh(on_device(vertices), on_device(faces), on_device(colours.astype(np.float32) / np.float32(255.0)), on_device(normals))
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out, stats = rf.simplify_mesh(mesh, config["cell_size"], target_faces=config["target_faces"], placement=config["placement"],
+                                  regularisation=config["regularisation"], return_stats=True)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    os.makedirs(os.path.dirname(os.path.abspath(config["output_path"])), exist_ok=True)
+    rf.write_ply(out, config["output_path"])
+    print(f"{config['placement']}, cell size {stats.cell_size:.6g}: V = {len(mesh.vertices)} -> {len(out.vertices)}, T = {len(mesh.faces)} -> {len(out.faces)} "
+          f"({stats.collapsed_faces} collapsed, {stats.merged_duplicates} duplicates merged, {stats.clusters} occupied cells) "
+          f"in {1e3 * dt:.1f} ms (incl. host synchronisation) -> {config['output_path']}")
+
+
+if __name__ == "__main__":
+    main()

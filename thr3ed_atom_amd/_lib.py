@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -31,6 +31,9 @@ SSIM_WINDOW = 11
 VQ_MAX_DIM, VQ_MAX_CODES = 64, 65536  # rf_vq_assign / rf_vq_centroids
 COMPONENT_TILE = 8  # kComponentTile of csrc/component_kernels.hip: edge of the node tiles rf_label_components labels in LDS
 CONNECTIVITIES = (6, 18, 26)  # rf_label_components
+MESH_PLACEMENTS = {"quadric": 0, "mean": 1}  # RF_MESH_PLACEMENT_*
+MESH_MAX_CELLS = 1 << 20  # per axis (rf_mesh_cluster_keys)
+MESH_CLUSTER_GROUP, MESH_CLUSTERS_PER_BLOCK, MESH_LONG_SEGMENT = 16, 16, 256  # kClusterGroup, kClustersPerBlock, kLongSegment of csrc/mesh_simplify_kernels.hip
 SSIM_TILE = (16, 32)  # map rows x columns per workgroup of rf_ssim_forward (image rows x columns of rf_ssim_backward)
 STEP_FORWARD = 1
 STEP_EMIT = 2
@@ -96,6 +99,8 @@ EXPORTED_SYMBOLS = [
     "rf_vq_assign",
     "rf_vq_centroids",
     "rf_label_components",
+    "rf_mesh_cluster_keys",
+    "rf_mesh_cluster_vertices",
 ]
 
 
@@ -369,6 +374,10 @@ def load() -> C.CDLL:
     lib.rf_vq_centroids.argtypes = [vp, i64, i32, vp, vp, vp, i32, vp, vp, vp]
     # connected components (csrc/component_kernels.hip)
     lib.rf_label_components.argtypes = [C.POINTER(RFGrid), f32, i32, vp, vp, vp]
+    # mesh simplification (csrc/mesh_simplify_kernels.hip)
+    i32p = C.POINTER(i32)
+    lib.rf_mesh_cluster_keys.argtypes = [vp, i64, fp, f32, i32p, vp, vp, vp]
+    lib.rf_mesh_cluster_vertices.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, fp, f32, i32p, i32, f32, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
             getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int

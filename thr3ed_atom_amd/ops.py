@@ -1404,6 +1404,67 @@ def label_components_raw(grid: VoxelGrid, threshold: float, connectivity: int, l
     _lib.check(rc, "rf_label_components")
 
 
+def _check_mesh_array(t: Tensor, dtype, cols: Optional[int], name: str) -> None:
+    _require_hip(t, name)
+    if t.dtype != dtype or not t.is_contiguous() or (t.dim() != 1 if cols is None else (t.dim() != 2 or t.shape[1] != cols)):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape " + ("[N]" if cols is None else f"[N, {cols}]"))
+
+
+def mesh_cluster_keys_raw(vertices: Tensor, origin, r: float, cells, keys: Tensor, status: Tensor) -> None:
+    """Enqueue rf_mesh_cluster_keys (include/relu_field.h): ``keys`` (int64 [V]) receives the cell key ``(k_x n_y + k_y) n_z + k_z`` of
+    every vertex of ``vertices`` (float32 [V, 3]) with ``k_a = floor(fl32(fl32(v_a - origin_a) * r))``, or -1 for a vertex outside the
+    ``cells`` = (n_x, n_y, n_z) cells (below ``origin``, NaN, infinite); ``status`` (int32 [1], zeroed by the caller) is set to 1 when
+    there is such a vertex.  ``origin`` and ``cells`` are host triples.  One launch, no host synchronisation.  No autograd."""
+    lib = _lib.load()
+    _check_mesh_array(vertices, torch.float32, 3, "vertices")
+    _check_mesh_array(keys, torch.int64, None, "keys")
+    _check_mesh_array(status, torch.int32, None, "status")
+    if keys.numel() != vertices.shape[0] or status.numel() < 1:
+        raise ValueError("keys must hold one int64 per vertex and status one int32")
+    with _span("mesh_cluster_keys", vertices.device):
+        rc = lib.rf_mesh_cluster_keys(vertices.data_ptr(), vertices.shape[0], _lib.float3(origin), float(r), (C.c_int32 * 3)(*[int(v) for v in cells]),
+                                      keys.data_ptr(), status.data_ptr(), _stream(vertices.device))
+    _lib.check(rc, "rf_mesh_cluster_keys")
+
+
+def mesh_cluster_vertices_raw(vertices: Tensor, colours: Optional[Tensor], normals: Optional[Tensor], faces: Tensor, members: Tensor,
+                              member_begin: Tensor, corners: Tensor, corner_begin: Tensor, cluster_keys: Tensor, origin, h: float, cells,
+                              placement: str, regularisation: float, vertices_out: Tensor, colours_out: Optional[Tensor],
+                              normals_out: Optional[Tensor]) -> None:
+    """Enqueue rf_mesh_cluster_vertices (include/relu_field.h): the representative, mean colour and normalised normal sum of every
+    cluster into ``vertices_out`` / ``colours_out`` / ``normals_out`` (float32 [C, 3]; an attribute is given on both sides or on
+    neither).  ``members`` (int64 [V]) lists the vertex indices stably sorted by cluster, ``corners`` (int64 [3 T]) the corner ids
+    ``3 f + j`` stably sorted by the cluster of their vertex, ``member_begin`` / ``corner_begin`` (int64 [C + 1]) bound every cluster's
+    segment, ``cluster_keys`` (int64 [C]) are the distinct cell keys in ascending order.  One launch, no atomics, reproducible bits,
+    no host synchronisation.  No autograd."""
+    lib = _lib.load()
+    if placement not in _lib.MESH_PLACEMENTS:
+        raise ValueError(f"placement must be one of {sorted(_lib.MESH_PLACEMENTS)}, got {placement!r}")
+    _check_mesh_array(vertices, torch.float32, 3, "vertices")
+    _check_mesh_array(faces, torch.int64, 3, "faces")
+    _check_mesh_array(cluster_keys, torch.int64, None, "cluster_keys")
+    num_vertices, num_faces, num_clusters = vertices.shape[0], faces.shape[0], cluster_keys.numel()
+    for t, n, name in ((members, num_vertices, "members"), (corners, 3 * num_faces, "corners"), (member_begin, num_clusters + 1, "member_begin"),
+                       (corner_begin, num_clusters + 1, "corner_begin")):
+        _check_mesh_array(t, torch.int64, None, name)
+        if t.numel() != n:
+            raise ValueError(f"{name} must hold {n} elements, got {t.numel()}")
+    for t, n, name in ((colours, num_vertices, "colours"), (normals, num_vertices, "normals"), (vertices_out, num_clusters, "vertices_out"),
+                       (colours_out, num_clusters, "colours_out"), (normals_out, num_clusters, "normals_out")):
+        if t is not None:
+            _check_mesh_array(t, torch.float32, 3, name)
+            if t.shape[0] != n:
+                raise ValueError(f"{name} must hold {n} rows, got {t.shape[0]}")
+    if (colours is None) != (colours_out is None) or (normals is None) != (normals_out is None):
+        raise ValueError("an attribute is given as input and output or as neither")
+    with _span("mesh_cluster_vertices", vertices.device):
+        rc = lib.rf_mesh_cluster_vertices(vertices.data_ptr(), _ptr(colours), _ptr(normals), num_vertices, faces.data_ptr(), num_faces, members.data_ptr(),
+                                          member_begin.data_ptr(), corners.data_ptr(), corner_begin.data_ptr(), cluster_keys.data_ptr(), num_clusters,
+                                          _lib.float3(origin), float(h), (C.c_int32 * 3)(*[int(v) for v in cells]), _lib.MESH_PLACEMENTS[placement],
+                                          float(regularisation), vertices_out.data_ptr(), _ptr(colours_out), _ptr(normals_out), _stream(vertices.device))
+    _lib.check(rc, "rf_mesh_cluster_vertices")
+
+
 def resample_grid_raw(src: VoxelGrid, dst: VoxelGrid, scale, offset, fill_density: float = 0.0) -> None:
     """Enqueue rf_resample_grid (include/relu_field.h): overwrite the tensors of ``dst`` with the raw channels of ``src`` at the
     continuous source indices ``s_a = fma(scale_a, i_a, offset_a)`` of its nodes (trilinear; ``(fill_density, 0 ...)`` outside the
