@@ -671,6 +671,34 @@ int rf_mesh_cluster_vertices(const float* vertices_dev, const float* colours_dev
                              const float* origin, float h, const int32_t* cells, int32_t placement, float regularisation,
                              float* vertices_out_dev, float* colours_out_dev, float* normals_out_dev, void* stream);
 
+/* ---- texture baking of a field onto a triangle mesh (csrc/texture_kernels.hip; thr3ed_atom_amd/texture.py
+ * lays the atlas out, computes the UVs and writes the OBJ / MTL / PNG) -------------------------------------------------------------
+ * Any indexed triangle mesh: vertices_dev [V, 3] float32, faces_dev [T, 3] int64.  The atlas is a uniform per-triangle one: blocks
+ * of B = patch + 4 texels square, `cols` x `rows` of them, block b at column (b % cols) B and row (b / cols) B of the image, holding
+ * triangle 2 b (lower) and 2 b + 1 (upper).  Texel (i, j) of a block (i the column, j the row, centre at (i, j)) belongs to the lower
+ * triangle when i + j <= patch + 3, else to the upper one; a triangle index >= num_faces leaves it UNOWNED.  The corners (v0, v1, v2)
+ * sit at (1, 1), (P, 1), (1, P) (lower) and (P + 2, P + 2), (3, P + 2), (P + 2, 3) (upper); with (a, b) the texel centre minus corner 0
+ * along the patch's legs, beta1 = a / (P - 1), beta2 = b / (P - 1), beta0 = 1 - beta1 - beta2, the texel's point is
+ * p = beta0 v0 + beta1 v1 + beta2 v2 (owned texels outside the triangle: the same affine map).
+ *   n = the unit normal (v1 - v0) x (v2 - v0), (0, 0, 0) for a zero-area triangle; D = 2 reach / samples; for s = 0 .. samples - 1
+ *   q_s = p + (reach - (s + 1/2) D) n; sigma_s = the renderer's activated density at q_s (grid's density_mode and density_scale; 0 on
+ *   or outside the AABB, strict test); alpha_s = 1 - exp(-sigma_s D); w_s = alpha_s prod_{r<s} (1 - alpha_r);
+ *   c(x) = sigmoid(sum_k Y_k(-n) f_k(x)) per colour on the features interpolated as rf_grid_query does (zero padding, no AABB test);
+ *   under RF_FLAG_RENDER_DIFFUSE c(x) = sigmoid(C0 f_0(x)) and split / bricked storage is read in its base record only.
+ *   texture_dev [rows B, cols B, 3] = sum_s w_s c(q_s) + (1 - sum_s w_s) c(p);  opacity_dev [rows B, cols B] (optional) = sum_s w_s.
+ *   Unowned texels are 0 in both images.  reach == 0 gives exactly c(p).
+ * ONE launch writes every texel of both images (no memset needed), one lane per texel, no atomics: two calls give identical bits.
+ * Every storage layout, density mode and SH degree 0-3.  A face index outside [0, num_vertices) sets status_dev[0] (int32, zeroed by
+ * the caller) to 1 and its texels to 0; it is never dereferenced.  Before any launch, in this order: RF_ERR_NULL_POINTER (grid, its
+ * tensors, texture_dev, status_dev, vertices_dev / faces_dev with a non-zero count), RF_ERR_BAD_SHAPE (grid dims, negative counts,
+ * patch outside [2, 64], samples outside [1, 256], a negative or non-finite reach, cols or rows < 1, an image edge above 16384,
+ * 2 cols rows < num_faces), RF_ERR_UNSUPPORTED (num_features, density_mode, layout, a flag bit other than RF_FLAG_RENDER_DIFFUSE).
+ * num_faces == 0 with a valid shape still clears the images.  (Added to ABI version 4 compatibly: no existing struct or signature
+ * changed.) */
+int rf_texture_bake(const RFGrid* grid, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces, int32_t patch,
+                    int32_t cols, int32_t rows, float reach, int32_t samples, uint32_t flags, float* texture_dev, float* opacity_dev, int32_t* status_dev,
+                    void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

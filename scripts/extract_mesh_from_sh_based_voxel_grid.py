@@ -13,6 +13,11 @@ reference load (create_volumetric_model_from_saved_model maps the reference's pi
 clustering with quadric-error representatives): cells of X * min(voxel_size) that start at the grid's AABB minimum, so the clusters
 align with the voxels, or the finest cells that leave at most N faces.  Off by default.
 
+--texture_patch P also writes a textured OBJ beside the PLY (mesh.obj, mesh.mtl, mesh.png for -o mesh.ply): the appearance of the field
+baked onto the written mesh -- after the simplification when that is on -- by thr3ed_atom_amd.texture with P texel centres per triangle
+leg, --texture_samples samples per texel and a ray of --texture_reach_voxels (smallest) voxel edges to either side of the surface
+(default: the simplification cell plus one voxel; two voxels without simplification).  Unset, nothing changes.
+
 --keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
 whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
 not touched.
@@ -46,6 +51,9 @@ import thr3ed_atom_amd as rf  # noqa: E402
               help="simplify the mesh by vertex clustering with cells of this many (smallest) voxel edges, aligned with the grid")
 @click.option("--target_faces", type=click.IntRange(min=0), default=None, required=False, help="simplify the mesh to at most this many faces")
 @click.option("--simplify_placement", type=click.Choice(["quadric", "mean"]), default="quadric", required=False, help="where a cluster's vertex goes")
+@click.option("--texture_patch", type=click.IntRange(min=2, max=64), default=None, required=False, help="also write a textured OBJ with this many texel centres per triangle leg")
+@click.option("--texture_reach_voxels", type=click.FloatRange(min=0.0), default=None, required=False, help="half length of a texel's ray, in (smallest) voxel edges")
+@click.option("--texture_samples", type=click.IntRange(min=1, max=256), default=16, required=False, help="samples per texel")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -70,6 +78,7 @@ def main(**kwargs) -> None:
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     extracted, summary = (len(mesh.vertices), len(mesh.faces)), ""
+    cell_voxels = None
     if (config["simplify_voxels"] is not None or config["target_faces"] is not None) and len(mesh.faces):
         t1 = time.perf_counter()
         if config["target_faces"] is not None:
@@ -84,12 +93,24 @@ def main(**kwargs) -> None:
             origin = np.where(origin > lowest, origin - h, origin).astype(np.float32)  # (float32 rounding of the step)
             mesh, stats = rf.simplify_mesh(mesh, float(h), origin=origin.tolist(), placement=config["simplify_placement"], return_stats=True)
         torch.cuda.synchronize()
+        cell_voxels = stats.cell_size / min(grid.voxel_size)
         summary = (f"simplified ({config['simplify_placement']}, cell size {stats.cell_size:.6g}): V = {extracted[0]} -> {len(mesh.vertices)}, "
                    f"T = {extracted[1]} -> {len(mesh.faces)} in {1e3 * (time.perf_counter() - t1):.1f} ms\n")
     out_dir = os.path.dirname(os.path.abspath(config["output_path"]))
     os.makedirs(out_dir, exist_ok=True)
     rf.write_ply(mesh, config["output_path"])
     print(summary, end="")
+    if config["texture_patch"] is not None and len(mesh.faces):
+        reach_voxels = config["texture_reach_voxels"]
+        if reach_voxels is None:
+            reach_voxels = 2.0 if cell_voxels is None else cell_voxels + 1.0
+        t2 = time.perf_counter()
+        bake = rf.bake_texture(mesh, grid, config["texture_patch"], reach=reach_voxels * min(grid.voxel_size), samples=config["texture_samples"], opacity=False)
+        torch.cuda.synchronize()
+        stem = os.path.splitext(config["output_path"])[0]
+        rf.write_obj(mesh, bake, stem)
+        print(f"texture: atlas {bake.cols * bake.block} x {bake.rows * bake.block} (patch {bake.patch}), reach {reach_voxels:.4g} voxels, {config['texture_samples']} samples "
+              f"in {1e3 * (time.perf_counter() - t2):.1f} ms -> {stem}.obj / .mtl / .png")
     print(f"grid {grid.grid_dims}, iso_level {iso:.6g}, subdivisions {config['subdivisions']}: V = {extracted[0]}, T = {extracted[1]} "
           f"in {1e3 * dt:.1f} ms (extraction incl. host synchronisation) -> {config['output_path']}")
 

@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -34,6 +34,7 @@ CONNECTIVITIES = (6, 18, 26)  # rf_label_components
 MESH_PLACEMENTS = {"quadric": 0, "mean": 1}  # RF_MESH_PLACEMENT_*
 MESH_MAX_CELLS = 1 << 20  # per axis (rf_mesh_cluster_keys)
 MESH_CLUSTER_GROUP, MESH_CLUSTERS_PER_BLOCK, MESH_LONG_SEGMENT = 16, 16, 256  # kClusterGroup, kClustersPerBlock, kLongSegment of csrc/mesh_simplify_kernels.hip
+TEXTURE_MIN_PATCH, TEXTURE_MAX_PATCH, TEXTURE_GUTTER, TEXTURE_MAX_SAMPLES, TEXTURE_MAX_EDGE = 2, 64, 4, 256, 16384  # rf_texture_bake (csrc/texture_kernels.hip): block edge = patch + gutter
 SSIM_TILE = (16, 32)  # map rows x columns per workgroup of rf_ssim_forward (image rows x columns of rf_ssim_backward)
 STEP_FORWARD = 1
 STEP_EMIT = 2
@@ -101,6 +102,7 @@ EXPORTED_SYMBOLS = [
     "rf_label_components",
     "rf_mesh_cluster_keys",
     "rf_mesh_cluster_vertices",
+    "rf_texture_bake",
 ]
 
 
@@ -378,6 +380,8 @@ def load() -> C.CDLL:
     i32p = C.POINTER(i32)
     lib.rf_mesh_cluster_keys.argtypes = [vp, i64, fp, f32, i32p, vp, vp, vp]
     lib.rf_mesh_cluster_vertices.argtypes = [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, fp, f32, i32p, i32, f32, vp, vp, vp, vp]
+    # texture baking (csrc/texture_kernels.hip)
+    lib.rf_texture_bake.argtypes = [C.POINTER(RFGrid), vp, i64, vp, i64, i32, i32, i32, f32, i32, u32, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
             getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int

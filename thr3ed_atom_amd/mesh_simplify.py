@@ -8,7 +8,7 @@ rewrite are torch ops on the device.  The result is a function of the input alon
 index for index by the float64 model of tests/mesh_simplify_model.py.  DESIGN.md section 20 has the contract and the measurements.
 
 Not done here: opposed pairs (a, b, c) and (a, c, b) -- a thin sheet whose two sides fell into the same cells -- both survive;
-edge-collapse simplification and UV texture baking are other tools."""
+edge-collapse simplification is another tool (texture baking: thr3ed_atom_amd/texture.py)."""
 import math
 from typing import NamedTuple, Optional
 
