@@ -699,6 +699,44 @@ int rf_texture_bake(const RFGrid* grid, const float* vertices_dev, int64_t num_v
                     int32_t cols, int32_t rows, float reach, int32_t samples, uint32_t flags, float* texture_dev, float* opacity_dev, int32_t* status_dev,
                     void* stream);
 
+/* ---- a rasteriser for triangle meshes (csrc/mesh_raster_kernels.hip; thr3ed_atom_amd/mesh_raster.py allocates
+ * the buffers and compares the result with the field's own render) ------------------------------------------------------------------
+ * Any indexed triangle mesh: vertices_dev [V, 3] float32, faces_dev [T, 3] int64; `camera` a HOST RFCamera.  Pixel (i, j) has the ray
+ * of rf_cast_rays, the same float32 operations in the same order: o = t, d = R ((j + 1/2 - W/2) / f, -(i + 1/2 - H/2) / f, -1).  With
+ * p_k = v_k - o: e0 = d . (p1 x p2), e1 = d . (p2 x p0), e2 = d . (p0 x p1), every cross product evaluated from the lower to the higher
+ * vertex index of its edge and negated when the face runs the other way, so that two faces sharing an edge see e and -e bit for bit
+ * (the library is built with -ffp-contract=off).  s = (e0 + e1) + e2.
+ *   The ray HITS the face when all e_k >= 0 or all e_k <= 0, and s != 0: edges are inclusive, zero-area and edge-on faces are never
+ *   drawn.  With (v1 - v0) x (v2 - v0) pointing out of the solid (the orientation of extract_mesh) a face seen from outside has
+ *   s < 0; under RF_RASTER_CULL_BACKFACES only s < 0 counts.  w_k = e_k / s.  z_k = the camera depth of corner k = -(p_k . R[:, 2]);
+ *   z = z0 + (w1 (z1 - z0) + w2 (z2 - z0)), the ray parameter of the hit (what RenderOut.depth holds).  A face with any z_k < near is
+ *   not drawn at all (not clipped).  A hit whose z is negative or not finite is no hit.
+ * rf_mesh_raster_visibility: visibility_dev [H, W] uint64, set to all ones by the CALLER (all ones = no hit); every hit does a
+ *   device-scope 64-bit atomic minimum of float_bits(z) << 32 | face.  The minimum does not depend on the order of arrival and the
+ *   lower face index wins exact depth ties: two calls give identical bits.  One lane per face; a face whose conservative pixel box
+ *   is at most 8 x 8 pixels is walked by its lane, larger boxes by the whole wavefront in 8 x 8 blocks.  A face index outside
+ *   [0, num_vertices) sets status_dev[0] (int32, zeroed by the caller) to 1 and the face is skipped; it is never dereferenced.
+ *   num_faces == 0 returns RF_OK without a launch.
+ * rf_mesh_raster_shade: one lane per pixel, no atomics.  depth_dev [H, W] = z, face_ids_dev [H, W] int32 = the face (0 and -1 where
+ *   nothing was hit), barycentrics_dev [H, W, 3] (optional) = w (0 where nothing was hit), re-evaluated by the same code as the
+ *   visibility pass (the same bits).  colour_dev [H, W, 3] (optional): with uvs_dev [T, 3, 2] and texture_dev [H_t, W_t, 3] (both or
+ *   neither; image row 0 on top, v = 1 there) the bilinear fetch at texel coordinates (u W_t - 1/2, (1 - v) H_t - 1/2) of the
+ *   interpolated (u, v) = sum_k w_k uv_k, taps clamped to the image; else sum_k w_k colours_dev[v_k] (colours_dev [V, 3]).  The texture
+ *   wins when both are given.  Pixels without a hit get 0, or 1 under RF_FLAG_WHITE_BKGD.  Both calls take the same camera, mesh and
+ *   flag word.
+ * Before any launch, in this order: RF_ERR_NULL_POINTER (camera, visibility_dev, status_dev / depth_dev, face_ids_dev, vertices_dev /
+ * faces_dev with a non-zero count, uvs_dev and texture_dev given by halves, colour_dev without a texture or colours_dev);
+ * RF_ERR_BAD_SHAPE (negative counts, num_faces >= 2^31, an image edge outside [1, 16384], a focal that is not finite or <= 0, a pose
+ * that is not finite, a near that is not finite or < 0, a texture edge outside [1, 16384]); RF_ERR_UNSUPPORTED (a flag bit other than
+ * RF_FLAG_WHITE_BKGD and RF_RASTER_CULL_BACKFACES).  (Added to ABI version 4 compatibly: no existing struct or signature changed.) */
+enum { RF_RASTER_CULL_BACKFACES = 32 };
+int rf_mesh_raster_visibility(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                              float near, uint32_t flags, uint64_t* visibility_dev, int32_t* status_dev, void* stream);
+int rf_mesh_raster_shade(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                         const uint64_t* visibility_dev, const float* uvs_dev, const float* texture_dev, int32_t texture_height, int32_t texture_width,
+                         const float* colours_dev, uint32_t flags, float* colour_dev, float* depth_dev, int32_t* face_ids_dev, float* barycentrics_dev,
+                         void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

@@ -1,0 +1,376 @@
+// mesh_raster_kernels.hip -- a rasteriser for exported triangle meshes (rf_mesh_raster_visibility / rf_mesh_raster_shade of
+// relu_field.h): what thr3ed_atom_amd/mesh_raster.py is built on.  DESIGN.md section 22 has the contract, docs/mesh_raster_errors.md
+// the error bound, tests/mesh_raster_model.py the float64 model.
+//
+// The ray.  Pixel (i, j) has exactly the ray cast_rays gives it: o = t, d = pixel_ray(i, j) of rf_device.h (the same float32
+// operations in the same order).  With p_k = v_k - o the edge values of the ray are the triple products e0 = d . (p1 x p2),
+// e1 = d . (p2 x p0), e2 = d . (p0 x p1); s = (e0 + e1) + e2 = d . ((v1 - v0) x (v2 - v0)) up to rounding.
+//
+// Watertight edges.  Every component of a cross product is ONE subtraction of two products and the library is built with
+// -ffp-contract=off, so p_a x p_b = -(p_b x p_a) holds bit for bit, and so does the dot product with d.  The kernels do not lean on
+// the compiler keeping that symmetry through two differently ordered call sites: every edge is evaluated from its LOWER to its
+// HIGHER vertex index and the sign is flipped afterwards when the face runs the other way.  Two faces that share an edge therefore
+// see e and -e, never e and -e(1 + ulp): a ray is on the inner side of exactly one of them, or exactly on the edge of both -- no
+// crack, no double cover away from the edge, and no fill-rule table.
+//
+// Coverage.  A ray hits when all three e are >= 0 or all three are <= 0, and s != 0 (edges inclusive; zero-area and edge-on faces
+// have s == 0 and are never drawn).  Mesh.faces has (v1 - v0) x (v2 - v0) pointing OUT of the solid, so a face seen from outside has
+// s < 0: under RF_RASTER_CULL_BACKFACES only s < 0 counts.  w_k = e_k / s.  z_k = the camera depth of corner k, the component of p_k
+// along -R[:, 2]; z = z0 + (w1 (z1 - z0) + w2 (z2 - z0)) -- sum_k w_k z_k anchored at corner 0, so that a face at one camera depth has
+// that depth exactly -- is the ray parameter of the hit, the quantity RenderOut.depth holds.  A face with any z_k < near is not drawn
+// at all (the documented rule; not a clip).
+//
+// The visibility pass.  One uint64 per pixel, float_bits(z) << 32 | face, all ones = nothing; device-scope 64-bit atomicMin without
+// a return value.  z >= 0, so its bits order like the number; the minimum does not depend on the order of arrival and the lower
+// face index wins exact ties: two runs give the same bits.  A relaxed pre-read skips the atomic when the stored key is already
+// smaller (the key only ever decreases).  Each lane sets up ONE face: bounds check (a bad face sets the status word and is skipped,
+// never dereferenced), corners, depth rule, the conservative pixel box of the three projected corners clipped to the image.  A box
+// of at most 8 x 8 pixels is walked by its own lane.  Larger boxes are handed to the whole wavefront one after another by ballot;
+// its 64 lanes cover the box in blocks of 8 x 8 pixels.  No LDS, no barrier, no workgroup waits for another.  A face is only ever
+// tested inside its box: a zero-area sliver whose edge values are rounding noise can be drawn at a pixel of its own projection, never
+// across the frame.
+//
+// The shade pass.  One lane per pixel, no atomics: decode the key, re-evaluate e, w, z of the winning face with the SAME device
+// functions (the same bits), write depth, face_ids, optionally the barycentrics, and the colour: a bilinear fetch of the bake's
+// texture at the interpolated per-corner UVs (texel coordinates (u W_t - 1/2, (1 - v) H_t - 1/2), taps clamped to the image), or
+// sum_k w_k colour_k of the vertex colours.  Pixels without a hit get the background, depth 0 and face id -1.
+#include "rf_device.h"
+
+namespace {
+
+constexpr int kRasterBlock = 256;
+constexpr int kMaxImageEdge = 16384;
+constexpr int kLaneBox = 8;  // boxes of at most kLaneBox x kLaneBox pixels stay on their lane; the wave path walks blocks of this edge
+constexpr unsigned long long kNoHit = ~0ull;
+
+struct RasterCamera {
+  int H, W;
+  float focal;
+  float R[9], t[3];
+};
+
+struct RasterArgs {
+  RasterCamera cam;
+  const float* vertices;
+  const long long* faces;
+  long long num_vertices, num_faces;
+  float near;
+  int cull;
+};
+
+// one face as a ray sees it: c[k] = the cross product of edge k's corners taken from the lower to the higher vertex index, flip[k]
+// whether the face runs along that edge the other way; zk[k] the camera depths
+struct RasterFace {
+  float c[3][3];
+  bool flip[3];
+  float zk[3];
+};
+
+__device__ __forceinline__ void cross3(const float* a, const float* b, float* out) {
+  out[0] = a[1] * b[2] - a[2] * b[1];
+  out[1] = a[2] * b[0] - a[0] * b[2];
+  out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// vi: the three vertex indices (checked by the caller), v: their positions
+__device__ __forceinline__ RasterFace raster_face(const RasterCamera& cam, const unsigned long long (&vi)[3], const float (&v)[3][3]) {
+  RasterFace f;
+  float p[3][3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int x = 0; x < 3; ++x) p[k][x] = v[k][x] - cam.t[x];
+    f.zk[k] = -((p[k][0] * cam.R[2] + p[k][1] * cam.R[5]) + p[k][2] * cam.R[8]);
+  }
+  // edge k runs from corner (k + 1) % 3 to corner (k + 2) % 3; evaluated from the lower to the higher vertex index (see the top)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int a = (k + 1) % 3, b = (k + 2) % 3;
+    f.flip[k] = vi[a] > vi[b];
+    if (f.flip[k])
+      cross3(p[b], p[a], f.c[k]);
+    else
+      cross3(p[a], p[b], f.c[k]);
+  }
+  return f;
+}
+
+struct RasterHit {
+  bool hit;
+  float w[3], z;
+};
+
+// the coverage rule, the barycentrics and the depth of pixel (i, j) on one face: the ONLY place they are computed
+__device__ __forceinline__ RasterHit raster_hit(const RasterCamera& cam, const RasterFace& f, int i, int j, int cull) {
+  float d[3], e[3];
+  pixel_ray(i, j, cam.H, cam.W, cam.focal, cam.R, d);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float t = (f.c[k][0] * d[0] + f.c[k][1] * d[1]) + f.c[k][2] * d[2];
+    e[k] = f.flip[k] ? -t : t;
+  }
+  const float s = (e[0] + e[1]) + e[2];
+  const bool neg = e[0] <= 0.0f && e[1] <= 0.0f && e[2] <= 0.0f, pos = e[0] >= 0.0f && e[1] >= 0.0f && e[2] >= 0.0f;
+  RasterHit h;
+  h.hit = (neg || (pos && !cull)) && s != 0.0f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) h.w[k] = e[k] / s;
+  h.z = f.zk[0] + (h.w[1] * (f.zk[1] - f.zk[0]) + h.w[2] * (f.zk[2] - f.zk[0]));
+  h.hit = h.hit && h.z >= 0.0f && h.z <= 3.0e38f;  // (a depth whose bits would not order like the number is no hit; NaN fails both)
+  return h;
+}
+
+// loads face t: false (and the status word set) when it indexes outside the vertices
+__device__ __forceinline__ bool load_face(const RasterArgs& a, long long t, unsigned long long (&vi)[3], float (&v)[3][3], int* status) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) vi[c] = (unsigned long long)a.faces[3 * t + c];
+  const unsigned long long V = (unsigned long long)a.num_vertices;
+  if (vi[0] >= V || vi[1] >= V || vi[2] >= V) {
+    if (status) *status = 1;  // (a plain store of one value: whichever lane wins, the word reads 1)
+    return false;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int x = 0; x < 3; ++x) v[c][x] = a.vertices[3 * vi[c] + x];
+  return true;
+}
+
+// The conservative pixel box [j0, j1] x [i0, i1] of a face whose corners all have z_k >= near >= 0: the projected corners, widened by
+// a bound on the float32 error of the projection plus one pixel, clipped to the image.  A corner whose depth is not safely positive
+// (or anything not finite) gives the whole image: conservative is all the box has to be, the coverage rule decides.
+__device__ __forceinline__ void raster_box(const RasterCamera& cam, const float (&v)[3][3], int& j0, int& j1, int& i0, int& i1) {
+  float xlo = 3.0e38f, xhi = -3.0e38f, ylo = 3.0e38f, yhi = -3.0e38f;
+  bool whole = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float p[3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) p[x] = v[k][x] - cam.t[x];
+    const float xc = (p[0] * cam.R[0] + p[1] * cam.R[3]) + p[2] * cam.R[6];
+    const float yc = (p[0] * cam.R[1] + p[1] * cam.R[4]) + p[2] * cam.R[7];
+    const float zc = -((p[0] * cam.R[2] + p[1] * cam.R[5]) + p[2] * cam.R[8]);
+    const float mag = (fabsf(p[0]) + fabsf(p[1])) + fabsf(p[2]);
+    const float rmax = fmaxf(fmaxf(fmaxf(fabsf(cam.R[0]), fabsf(cam.R[1])), fmaxf(fabsf(cam.R[2]), fabsf(cam.R[3]))),
+                             fmaxf(fmaxf(fabsf(cam.R[4]), fabsf(cam.R[5])), fmaxf(fmaxf(fabsf(cam.R[6]), fabsf(cam.R[7])), fabsf(cam.R[8]))));
+    const float del = 1.0e-6f * mag * rmax;  // > 4 ulp of every term of xc, yc, zc
+    if (!(zc - del > 0.0f)) {
+      whole = true;
+      continue;
+    }
+    const float inv = 1.0f / (zc - del);
+    const float x = cam.focal * xc / zc + (float)cam.W * 0.5f - 0.5f;
+    const float y = (float)cam.H * 0.5f - 0.5f - cam.focal * yc / zc;
+    const float ex = cam.focal * inv * (del + fabsf(xc) * inv * del) * 2.0f + 1.0e-6f * (fabsf(x) + (float)cam.W) + 1.0f;
+    const float ey = cam.focal * inv * (del + fabsf(yc) * inv * del) * 2.0f + 1.0e-6f * (fabsf(y) + (float)cam.H) + 1.0f;
+    if (!(fabsf(x) + ex < 1.0e9f) || !(fabsf(y) + ey < 1.0e9f)) {
+      whole = true;
+      continue;
+    }
+    xlo = fminf(xlo, x - ex), xhi = fmaxf(xhi, x + ex);
+    ylo = fminf(ylo, y - ey), yhi = fmaxf(yhi, y + ey);
+  }
+  if (whole) {
+    j0 = 0, j1 = cam.W - 1, i0 = 0, i1 = cam.H - 1;
+    return;
+  }
+  // (clamped as floats first: every value that is converted lies in [-1, edge])
+  j0 = (int)ceilf(fminf(fmaxf(xlo, 0.0f), (float)cam.W));
+  j1 = (int)floorf(fminf(fmaxf(xhi, -1.0f), (float)(cam.W - 1)));
+  i0 = (int)ceilf(fminf(fmaxf(ylo, 0.0f), (float)cam.H));
+  i1 = (int)floorf(fminf(fmaxf(yhi, -1.0f), (float)(cam.H - 1)));
+}
+
+__device__ __forceinline__ void raster_pixel(const RasterCamera& cam, const RasterFace& f, int i, int j, int cull, unsigned int face,
+                                             unsigned long long* vis) {
+  const RasterHit h = raster_hit(cam, f, i, j, cull);
+  if (!h.hit) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint(h.z) << 32) | (unsigned long long)face;
+  unsigned long long* slot = vis + ((long long)i * cam.W + j);
+  if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= key) return;  // the key only ever decreases
+  (void)__hip_atomic_fetch_min(slot, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ float shfl_f(float x, int src) { return __shfl(x, src, 64); }
+
+__global__ __launch_bounds__(kRasterBlock) void mesh_raster_visibility_kernel(RasterArgs a, unsigned long long* vis, int* status) {
+  const long long t = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
+  const int lane = (int)(threadIdx.x & 63);
+  // (no lane returns early: the ballot loop below needs the whole wavefront)
+  RasterFace f;
+  int j0 = 0, j1 = -1, i0 = 0, i1 = -1;
+  bool live = t < a.num_faces;
+  if (live) {
+    unsigned long long vi[3];
+    float v[3][3];
+    live = load_face(a, t, vi, v, status);
+    if (live) {
+      f = raster_face(a.cam, vi, v);
+      live = !(f.zk[0] < a.near) && !(f.zk[1] < a.near) && !(f.zk[2] < a.near);
+      if (live) {
+        raster_box(a.cam, v, j0, j1, i0, i1);
+        live = j0 <= j1 && i0 <= i1;
+      }
+    }
+  }
+  const bool small = live && (j1 - j0) < kLaneBox && (i1 - i0) < kLaneBox;
+  if (small) {
+    for (int i = i0; i <= i1; ++i)
+      for (int j = j0; j <= j1; ++j) raster_pixel(a.cam, f, i, j, a.cull, (unsigned int)t, vis);
+  }
+  unsigned long long todo = __ballot(live && !small);
+  while (todo) {  // (wave-uniform)
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    RasterFace g;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int x = 0; x < 3; ++x) g.c[k][x] = shfl_f(f.c[k][x], src);
+      g.flip[k] = __shfl((int)f.flip[k], src, 64) != 0;
+      g.zk[k] = shfl_f(f.zk[k], src);
+    }
+    const int bj0 = __shfl(j0, src, 64), bj1 = __shfl(j1, src, 64), bi0 = __shfl(i0, src, 64), bi1 = __shfl(i1, src, 64);
+    const unsigned int face = (unsigned int)(t - lane + src);
+    for (int bi = bi0; bi <= bi1; bi += kLaneBox)
+      for (int bj = bj0; bj <= bj1; bj += kLaneBox) {
+        const int i = bi + (lane >> 3), j = bj + (lane & 7);
+        if (i <= bi1 && j <= bj1) raster_pixel(a.cam, g, i, j, a.cull, face, vis);
+      }
+  }
+}
+
+struct ShadeArgs {
+  const unsigned long long* vis;
+  const float* uvs;      // [T, 3, 2] or nullptr
+  const float* texture;  // [Ht, Wt, 3] or nullptr
+  int Ht, Wt;
+  const float* colours;  // [V, 3] or nullptr
+  float background;
+  float* colour;  // or nullptr
+  float* depth;
+  int* face_ids;
+  float* bary;  // or nullptr
+};
+
+__global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterArgs a, ShadeArgs s) {
+  const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
+  if (pix >= (long long)a.cam.H * a.cam.W) return;
+  const int i = (int)(pix / a.cam.W), j = (int)(pix - (long long)i * a.cam.W);
+  const unsigned long long key = s.vis[pix];
+  float rgb[3] = {s.background, s.background, s.background}, w[3] = {0.0f, 0.0f, 0.0f}, z = 0.0f;
+  int id = -1;
+  const long long t = (long long)(key & 0xffffffffull);
+  if (key != kNoHit && t < a.num_faces) {
+    unsigned long long vi[3];
+    float v[3][3];
+    if (load_face(a, t, vi, v, nullptr)) {
+      const RasterFace f = raster_face(a.cam, vi, v);
+      const RasterHit h = raster_hit(a.cam, f, i, j, a.cull);  // the bits the visibility pass saw
+      id = (int)t, z = h.z;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) w[k] = h.w[k];
+      if (s.colour && s.texture) {
+        const float* uv = s.uvs + 6 * t;
+        const float u = (w[0] * uv[0] + w[1] * uv[2]) + w[2] * uv[4];
+        const float vv = (w[0] * uv[1] + w[1] * uv[3]) + w[2] * uv[5];
+        const float x = u * (float)s.Wt - 0.5f, y = (1.0f - vv) * (float)s.Ht - 0.5f;
+        const float xf = floorf(x), yf = floorf(y);
+        const float fx = x - xf, fy = y - yf;
+        // (clamped as floats first, so that the conversion is defined for every value; NaN goes to 0)
+        const int x0 = (int)fminf(fmaxf(xf, 0.0f), (float)(s.Wt - 1)), x1 = (int)fminf(fmaxf(xf + 1.0f, 0.0f), (float)(s.Wt - 1));
+        const int y0 = (int)fminf(fmaxf(yf, 0.0f), (float)(s.Ht - 1)), y1 = (int)fminf(fmaxf(yf + 1.0f, 0.0f), (float)(s.Ht - 1));
+        const float* r0 = s.texture + 3ll * ((long long)y0 * s.Wt);
+        const float* r1 = s.texture + 3ll * ((long long)y1 * s.Wt);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+          const float top = (1.0f - fx) * r0[3 * x0 + ch] + fx * r0[3 * x1 + ch];
+          const float bot = (1.0f - fx) * r1[3 * x0 + ch] + fx * r1[3 * x1 + ch];
+          rgb[ch] = (1.0f - fy) * top + fy * bot;
+        }
+      } else if (s.colour && s.colours) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          rgb[ch] = (w[0] * s.colours[3 * vi[0] + ch] + w[1] * s.colours[3 * vi[1] + ch]) + w[2] * s.colours[3 * vi[2] + ch];
+      }
+    }
+  }
+  s.depth[pix] = z;
+  s.face_ids[pix] = id;
+  if (s.colour) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) s.colour[3 * pix + ch] = rgb[ch];
+  }
+  if (s.bary) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s.bary[3 * pix + k] = w[k];
+  }
+}
+
+// the checks both entry points share, after their pointer checks: RF_ERR_BAD_SHAPE, then RF_ERR_UNSUPPORTED
+int check_raster(const RFCamera* cam, int64_t num_vertices, int64_t num_faces, float near, uint32_t flags) {
+  if (num_vertices < 0 || num_faces < 0 || num_faces >= (1ll << 31)) return RF_ERR_BAD_SHAPE;
+  if (cam->height < 1 || cam->height > kMaxImageEdge || cam->width < 1 || cam->width > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
+  if (!std::isfinite(cam->focal) || !(cam->focal > 0.0f)) return RF_ERR_BAD_SHAPE;
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(cam->pose[k])) return RF_ERR_BAD_SHAPE;
+  if (!std::isfinite(near) || !(near >= 0.0f)) return RF_ERR_BAD_SHAPE;
+  if (flags & ~(uint32_t)(RF_FLAG_WHITE_BKGD | RF_RASTER_CULL_BACKFACES)) return RF_ERR_UNSUPPORTED;
+  return RF_OK;
+}
+
+RasterArgs raster_args(const RFCamera* cam, const float* vertices, int64_t num_vertices, const int64_t* faces, int64_t num_faces, float near, uint32_t flags) {
+  RasterArgs a;
+  a.cam.H = cam->height, a.cam.W = cam->width, a.cam.focal = cam->focal;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) a.cam.R[3 * r + c] = cam->pose[4 * r + c];
+    a.cam.t[r] = cam->pose[4 * r + 3];
+  }
+  a.vertices = vertices, a.faces = (const long long*)faces;
+  a.num_vertices = num_vertices, a.num_faces = num_faces;
+  a.near = near, a.cull = (flags & RF_RASTER_CULL_BACKFACES) ? 1 : 0;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rf_mesh_raster_visibility(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                              float near, uint32_t flags, uint64_t* visibility_dev, int32_t* status_dev, void* stream) {
+  if (!camera || !visibility_dev || !status_dev) return RF_ERR_NULL_POINTER;
+  if ((num_vertices > 0 && !vertices_dev) || (num_faces > 0 && !faces_dev)) return RF_ERR_NULL_POINTER;
+  const int rc = check_raster(camera, num_vertices, num_faces, near, flags);
+  if (rc != RF_OK) return rc;
+  if (num_faces == 0) return RF_OK;
+  const RasterArgs a = raster_args(camera, vertices_dev, num_vertices, faces_dev, num_faces, near, flags);
+  const dim3 blocks((unsigned)((num_faces + kRasterBlock - 1) / kRasterBlock));  // < 2^23
+  hipLaunchKernelGGL(mesh_raster_visibility_kernel, blocks, dim3(kRasterBlock), 0, (hipStream_t)stream, a, (unsigned long long*)visibility_dev, status_dev);
+  return launch_status();
+}
+
+int rf_mesh_raster_shade(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                         const uint64_t* visibility_dev, const float* uvs_dev, const float* texture_dev, int32_t texture_height, int32_t texture_width,
+                         const float* colours_dev, uint32_t flags, float* colour_dev, float* depth_dev, int32_t* face_ids_dev, float* barycentrics_dev,
+                         void* stream) {
+  if (!camera || !visibility_dev || !depth_dev || !face_ids_dev) return RF_ERR_NULL_POINTER;
+  if ((num_vertices > 0 && !vertices_dev) || (num_faces > 0 && !faces_dev)) return RF_ERR_NULL_POINTER;
+  if ((uvs_dev == nullptr) != (texture_dev == nullptr)) return RF_ERR_NULL_POINTER;  // the bake's two halves come together
+  if (colour_dev && !texture_dev && !colours_dev) return RF_ERR_NULL_POINTER;        // a colour image needs a source
+  const int rc = check_raster(camera, num_vertices, num_faces, 0.0f, 0u);
+  if (rc != RF_OK) return rc;
+  if (texture_dev && (texture_height < 1 || texture_height > kMaxImageEdge || texture_width < 1 || texture_width > kMaxImageEdge)) return RF_ERR_BAD_SHAPE;
+  if (flags & ~(uint32_t)(RF_FLAG_WHITE_BKGD | RF_RASTER_CULL_BACKFACES)) return RF_ERR_UNSUPPORTED;
+  const RasterArgs a = raster_args(camera, vertices_dev, num_vertices, faces_dev, num_faces, 0.0f, flags);
+  ShadeArgs s;
+  s.vis = (const unsigned long long*)visibility_dev;
+  s.uvs = uvs_dev, s.texture = texture_dev, s.Ht = texture_height, s.Wt = texture_width;
+  s.colours = colours_dev;
+  s.background = (flags & RF_FLAG_WHITE_BKGD) ? 1.0f : 0.0f;
+  s.colour = colour_dev, s.depth = depth_dev, s.face_ids = face_ids_dev, s.bary = barycentrics_dev;
+  const long long total = (long long)camera->height * camera->width;  // <= 2^28
+  hipLaunchKernelGGL(mesh_raster_shade_kernel, dim3((unsigned)((total + kRasterBlock - 1) / kRasterBlock)), dim3(kRasterBlock), 0, (hipStream_t)stream, a, s);
+  return launch_status();
+}
+
+}  // extern "C"

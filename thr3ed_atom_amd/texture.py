@@ -7,7 +7,7 @@ independently in float64 numpy by tests/texture_model.py; DESIGN.md section 21 h
 docs/texture_errors.md the error bound.
 
 Not done here: chart atlases with shared seams, mip-safe gutters beyond the one texel this layout has, a normal map, baking by
-rendering from the training cameras, a mesh rasteriser."""
+rendering from the training cameras.  (The rasteriser that looks at the result is thr3ed_atom_amd/mesh_raster.py.)"""
 import ctypes as C
 import math
 import os
