@@ -737,6 +737,39 @@ int rf_mesh_raster_shade(const RFCamera* camera, const float* vertices_dev, int6
                          const float* colours_dev, uint32_t flags, float* colour_dev, float* depth_dev, int32_t* face_ids_dev, float* barycentrics_dev,
                          void* stream);
 
+/* ---- texture baking from posed views (csrc/texture_views_kernels.hip; thr3ed_atom_amd/texture.py chunks the
+ * views, runs rf_mesh_raster_visibility per view and finalises) ---------------------------------------------------------------------
+ * The mesh and the atlas (patch, cols, rows) are those of rf_texture_bake: the same texel -> face -> point p and unit normal n, bit
+ * for bit (n = 0 for a zero-area face, which no view ever counts).  `cameras` is a HOST array of num_views (0 .. 16) RFCamera of one
+ * height H and width W (focals and poses are free); images_dev [n, H, W, 3] float32; visibility_dev [n, H, W] uint64, exactly what
+ * rf_mesh_raster_visibility writes per view; alphas_dev [n, H, W] float32 or NULL.  accum_dev [rows B, cols B, 4] float32 (three colour
+ * sums and one weight sum) and the optional count_dev [rows B, cols B] int32 are IN/OUT.  Per owned texel, for each view k in order:
+ *   1. c = R_k^T (p - t_k), z = -c_z; rejected unless z is finite and z > near.
+ *   2. x = W/2 + f c_x / z, y = H/2 - f c_y / z (the inverse of the ray of rf_cast_rays: pixel (i, j) has its centre at (j + 1/2, i + 1/2));
+ *      rejected unless 0 <= x < W and 0 <= y < H; j = floor(x), i = floor(y).
+ *   3. key = visibility[k, i, j]; rejected when it is all ones; z_buf = the float in its high 32 bits; rejected unless
+ *      z <= z_buf + depth_bias (a shadow-map test with a bias; the face id in the low word is not used).
+ *   4. cos = n . (t_k - p) / |t_k - p|, |cos| under RF_TEXTURE_VIEWS_TWO_SIDED; rejected unless cos > min_cos; omega = cos^cos_power by
+ *      repeated multiplication (power 0 gives exactly 1).
+ *   5. C = the bilinear fetch of image k at (x - 1/2, y - 1/2), taps clamped to the image; m = the same fetch of the alpha plane, or 1.
+ *   6. accum.rgb += omega m (C - (1 - m) background), accum.w += omega m m, count += 1: the sums of the least-squares texel
+ *      sum omega m (C - (1 - m) background) / sum omega m^2 of pixels read as C = m c + (1 - m) background.
+ * One launch, one lane per texel, no atomics: the lane loads its accumulator words, adds its views in order and stores them, so two
+ * calls give identical bits and successive calls over chunks of views do the float additions of one long loop.  Unowned texels are
+ * not touched.  A face index outside [0, num_vertices) sets status_dev[0] (int32, zeroed by the caller) to 1 and leaves the face's
+ * texels as they were; it is never dereferenced.  Before any launch, in this order: RF_ERR_NULL_POINTER (accum_dev, status_dev,
+ * vertices_dev / faces_dev with a non-zero count, cameras / images_dev / visibility_dev with num_views > 0), RF_ERR_BAD_SHAPE (negative
+ * counts, num_views > 16, patch outside [2, 64], cols or rows < 1, an atlas or image edge outside [1, 16384], 2 cols rows < num_faces,
+ * views of unequal size, a focal that is not finite or <= 0, a pose that is not finite, near / depth_bias / background not finite or
+ * negative, min_cos outside [0, 1), cos_power outside [0, 8]), RF_ERR_UNSUPPORTED (a flag bit other than RF_TEXTURE_VIEWS_TWO_SIDED).
+ * num_views == 0 or num_faces == 0 returns RF_OK without a launch.  (Added to ABI version 4 compatibly: no existing struct or
+ * signature changed.) */
+enum { RF_TEXTURE_VIEWS_TWO_SIDED = 64 };
+int rf_texture_project_views(const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces, int32_t patch, int32_t cols,
+                             int32_t rows, int32_t num_views, const RFCamera* cameras, const float* images_dev, const uint64_t* visibility_dev,
+                             const float* alphas_dev, float near, float depth_bias, float min_cos, int32_t cos_power, float background, uint32_t flags,
+                             float* accum_dev, int32_t* count_dev, int32_t* status_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

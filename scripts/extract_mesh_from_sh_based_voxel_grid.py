@@ -17,6 +17,9 @@ align with the voxels, or the finest cells that leave at most N faces.  Off by d
 baked onto the written mesh -- after the simplification when that is on -- by thr3ed_atom_amd.texture with P texel centres per triangle
 leg, --texture_samples samples per texel and a ray of --texture_reach_voxels (smallest) voxel edges to either side of the surface
 (default: the simplification cell plus one voxel; two voxels without simplification).  Unset, nothing changes.
+--texture_views N (with --texture_patch) then re-bakes the texels a camera sees from the field's own renders over the turn-table of
+scripts/render_mesh.py with --num_frames N and the checkpoint's camera (rf.bake_texture_from_field_views); the
+texels no view sees keep the normal-ray bake.  scripts/bake_texture.py has the remaining options.
 
 --keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
 whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
@@ -54,6 +57,7 @@ import thr3ed_atom_amd as rf  # noqa: E402
 @click.option("--texture_patch", type=click.IntRange(min=2, max=64), default=None, required=False, help="also write a textured OBJ with this many texel centres per triangle leg")
 @click.option("--texture_reach_voxels", type=click.FloatRange(min=0.0), default=None, required=False, help="half length of a texel's ray, in (smallest) voxel edges")
 @click.option("--texture_samples", type=click.IntRange(min=1, max=256), default=16, required=False, help="samples per texel")
+@click.option("--texture_views", type=click.IntRange(min=2), default=None, required=False, help="with --texture_patch: re-bake the seen texels from the field's renders over a turn-table of this many frames")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -64,7 +68,9 @@ def main(**kwargs) -> None:
         raise click.UsageError("--keep_largest / --min_component_nodes need a non-negative --iso_level (the occupancy threshold of the components)")
     dev = torch.device("cuda:0")
     creator = lambda info: rf.create_voxel_grid_from_saved_info_dict(info, storage="split")  # noqa: E731
-    model, _ = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)
+    if config["texture_views"] is not None and config["texture_patch"] is None:
+        raise click.UsageError("--texture_views needs --texture_patch")
+    model, extra = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)
     grid = model.thre3d_repr
     iso = config["iso_level"]
     if iso is None:
@@ -106,6 +112,12 @@ def main(**kwargs) -> None:
             reach_voxels = 2.0 if cell_voxels is None else cell_voxels + 1.0
         t2 = time.perf_counter()
         bake = rf.bake_texture(mesh, grid, config["texture_patch"], reach=reach_voxels * min(grid.voxel_size), samples=config["texture_samples"], opacity=False)
+        if config["texture_views"] is not None:
+            intr = (extra or {}).get("camera_intrinsics", rf.CameraIntrinsics(800, 800, 1111.111))
+            poses = rf.get_thre360_animation_poses((extra or {}).get("hemispherical_radius", 4.0311), 60.0, config["texture_views"])
+            views = rf.bake_texture_from_field_views(mesh, model, poses, intr, config["texture_patch"], fallback=bake)
+            print(f"texture: {int((views.views > 0).sum())} texels re-baked from {len(poses)} renders of {intr[0]}x{intr[1]}")
+            bake = views.bake
         torch.cuda.synchronize()
         stem = os.path.splitext(config["output_path"])[0]
         rf.write_obj(mesh, bake, stem)

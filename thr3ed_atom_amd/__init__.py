@@ -47,7 +47,7 @@ from .composable import (  # noqa: F401  (the path at the granularity of the ref
 )
 from .mesh import Mesh, extract_mesh, write_ply  # noqa: F401
 from .mesh_simplify import MeshSimplifyStats, simplify_mesh  # noqa: F401
-from .texture import TextureBake, bake_texture, write_obj  # noqa: F401
+from .texture import TextureBake, ViewBake, bake_texture, bake_texture_from_field_views, bake_texture_from_views, write_obj  # noqa: F401
 from .mesh_raster import MeshRender, evaluate_mesh_against_field, read_obj, render_mesh  # noqa: F401
 from .ops import distortion_loss, render_geometry, total_variation  # noqa: F401
 from .metrics import ssim  # noqa: F401

@@ -24,6 +24,7 @@
 // record in split / bricked storage).  A face index outside [0, V) stores 1 to the status word and bakes zeros; it is never used
 // as an address.
 #include "rf_device.h"
+#include "texture_atlas.h"
 
 namespace {
 
@@ -98,49 +99,21 @@ __global__ __launch_bounds__(kBakeBlock) void texture_bake_kernel(GridArgs g_in,
   GridArgs g = g_in;
   g.F = 3 * K;  // (the host dispatched on it: a constant here, so that query_offset's divisions fold)
   const int B = a.block, P = a.patch;
-  const long long width = (long long)a.cols * B, total = width * ((long long)a.rows * B);
+  const long long total = ((long long)a.cols * B) * ((long long)a.rows * B);
   const long long t = (long long)blockIdx.x * kBakeBlock + threadIdx.x;
   if (t >= total) return;
-  const int bb = B * B;
-  const long long blk = t / bb;
-  const int r = (int)(t - blk * bb);
-  const int j = r / B, i = r - j * B;
-  const long long br = blk / a.cols, bc = blk - br * a.cols;
-  const long long col = bc * B + i, row = br * B + j;
-  const long long pixel = row * width + col;
-  const bool upper = i + j > P + 3;
-  const long long tri = 2 * blk + (upper ? 1 : 0);
+  const AtlasTexel tx = atlas_texel(t, P, B, a.cols);  // texture_atlas.h: the map the view projection shares
+  const long long pixel = tx.pixel;
   float out[3] = {0.0f, 0.0f, 0.0f}, opacity = 0.0f;
-  bool owned = tri < a.num_faces;
+  bool owned = tx.tri < a.num_faces;
   unsigned long long vi[3] = {0ull, 0ull, 0ull};
-  if (owned) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) vi[c] = (unsigned long long)a.faces[3 * tri + c];
-    if (vi[0] >= (unsigned long long)a.num_vertices || vi[1] >= (unsigned long long)a.num_vertices || vi[2] >= (unsigned long long)a.num_vertices) {
-      *a.status = 1;  // (a plain store of one value: whichever lane wins, the word reads 1)
-      owned = false;
-    }
+  if (owned && !atlas_face(a.faces, a.num_vertices, tx.tri, vi)) {
+    *a.status = 1;  // (a plain store of one value: whichever lane wins, the word reads 1)
+    owned = false;
   }
   if (owned) {
-    float v[3][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int x = 0; x < 3; ++x) v[c][x] = a.vertices[3 * vi[c] + x];
-    const float legs = (float)(P - 1);
-    const float b1 = (float)(upper ? P + 2 - i : i - 1) / legs, b2 = (float)(upper ? P + 2 - j : j - 1) / legs;
-    const float b0 = (1.0f - b1) - b2;
-    float p[3], e1[3], e2[3];
-#pragma unroll
-    for (int x = 0; x < 3; ++x) {
-      p[x] = (b0 * v[0][x] + b1 * v[1][x]) + b2 * v[2][x];
-      e1[x] = v[1][x] - v[0][x];
-      e2[x] = v[2][x] - v[0][x];
-    }
-    float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-    const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-#pragma unroll
-    for (int x = 0; x < 3; ++x) n[x] = (len > 0.0f) ? n[x] / len : 0.0f;
+    float p[3], n[3];
+    atlas_point(a.vertices, vi, P, tx, p, n);
     float Y[16];
     sh_basis<KE>(-n[0], -n[1], -n[2], Y);  // d = -n: a camera that faces the surface
     const float delta = (2.0f * a.reach) / (float)a.samples;
