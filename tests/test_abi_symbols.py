@@ -30,6 +30,80 @@ def test_every_declared_symbol_is_exported(lib):
     assert sorted(_lib.EXPORTED_SYMBOLS) == names
 
 
+def declared_prototypes():
+    """{name: (return type, [parameter types])} of include/relu_field.h: `type rf_name(type name, ...);`, comments removed"""
+    text = open(os.path.join(REPO, "include", "relu_field.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+    out = {}
+    for ret, name, params in re.findall(r"(?m)^((?:const )?\w+\*?) (rf_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", text):
+        params = [p.strip() for p in params.split(",")]
+        types = [] if params == ["void"] else [re.sub(r"\s*\b\w+$", "", p) for p in params]  # (drop the parameter's name)
+        assert name not in out and all(types), (name, params)
+        out[name] = (ret.strip(), types)
+    return out
+
+
+def _same_scalar(ctype, c_name):
+    """``ctype`` has the width, the signedness and the float-ness of the C scalar type ``c_name``"""
+    import ctypes as C
+
+    expected = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "float": C.c_float,
+                "int16_t": C.c_int16, "uint8_t": C.c_uint8}[c_name]
+    kind = lambda t: "float" if t._type_ in "fd" else "signed" if t._type_ in "bhilq" else "unsigned" if t._type_ in "BHILQ" else t._type_  # noqa: E731
+    return isinstance(ctype, type) and issubclass(ctype, C._SimpleCData) and C.sizeof(ctype) == C.sizeof(expected) and kind(ctype) == kind(expected)
+
+
+def _matches(ctype, c_type):
+    """one ``argtypes`` entry against one parameter type of the header"""
+    import ctypes as C
+
+    base = re.sub(r"\bconst\b|\*|\s", "", c_type)
+    depth = c_type.count("*")
+    if depth == 0:
+        return _same_scalar(ctype, base)
+    if depth == 1 and base.startswith("RF"):
+        return ctype is C.POINTER(getattr(_lib, base))  # a struct pointer: to the mirror of that struct
+    if ctype is C.c_void_p:
+        return True  # an untyped pointer stands for any pointer to scalars (device memory is passed as data_ptr())
+    if not hasattr(ctype, "contents"):
+        return False
+    if depth > 1:
+        return ctype._type_ is C.c_void_p
+    return base != "void" and _same_scalar(ctype._type_, base)
+
+
+def test_argtypes_agree_with_the_header(lib):
+    """Every prototype of relu_field.h against the hand-written ``argtypes`` / ``restype`` of ``_lib.load()``: the same number of
+    parameters, a pointer where the header has one (to the struct's mirror for a struct), the same width and signedness for a
+    scalar, the same return type.  Names and sizeof() alone (the tests above, ``load()`` itself) do not notice a wrong entry in
+    a 21-entry list; the call would corrupt its arguments silently."""
+    import ctypes as C
+
+    prototypes = declared_prototypes()
+    assert sorted(prototypes) == sorted(_lib.EXPORTED_SYMBOLS)
+    for name, (ret, params) in sorted(prototypes.items()):
+        fn = getattr(lib, name)
+        argtypes = fn.argtypes or []  # (rf_abi_version(void) has none)
+        assert len(argtypes) == len(params), f"{name}: {len(argtypes)} argtypes, {len(params)} parameters in the header"
+        for k, (ctype, c_type) in enumerate(zip(argtypes, params)):
+            assert _matches(ctype, c_type), f"{name}: argument {k} is {ctype!r}, the header has `{c_type}`"
+        if ret == "const char*":
+            assert fn.restype is C.c_char_p, name
+        else:
+            assert _same_scalar(fn.restype, ret), f"{name}: restype {fn.restype!r}, the header returns `{ret}`"
+
+
+def test_the_argtypes_check_notices_a_wrong_entry():
+    """the comparison itself: a narrower integer, another signedness, a scalar for a pointer and another struct are all refused"""
+    import ctypes as C
+
+    assert _matches(C.c_int64, "int64_t") and not _matches(C.c_int32, "int64_t") and not _matches(C.c_uint32, "int32_t")
+    assert not _matches(C.c_float, "int32_t") and not _matches(C.c_int64, "const float*") and not _matches(C.c_void_p, "int64_t")
+    assert _matches(C.POINTER(_lib.RFGrid), "const RFGrid*") and not _matches(C.POINTER(_lib.RFCamera), "const RFGrid*")
+    assert not _matches(C.c_void_p, "const RFGrid*") and _matches(C.POINTER(C.c_float), "const float*") and not _matches(C.POINTER(C.c_int32), "const float*")
+
+
 def test_abi_version_and_error_strings(lib):
     assert lib.rf_abi_version() == _lib.ABI_VERSION == 4
     assert lib.rf_error_string(0) == b"ok"

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _marshal
 from .voxels import VoxelGrid, as_kernel_grid, unpack_storage
 
 FORMAT_VERSION = 1  # of the payload of CompressedField.to_bytes(): the "version" field of its header
@@ -58,7 +58,7 @@ def vq_assign(vectors: Tensor, codebook: Tensor) -> Tuple[Tensor, Tensor]:
     index = torch.empty(M, dtype=torch.int32, device=vectors.device)
     dist = torch.empty(M, dtype=torch.float32, device=vectors.device)
     stride = vectors.stride(0) if M > 1 else D
-    stream = torch.cuda.current_stream(vectors.device).cuda_stream
+    stream = _marshal.stream(vectors.device)
     with torch.cuda.device(vectors.device):
         rc = _lib.load().rf_vq_assign(vectors.data_ptr() if M else None, M, D, stride, codebook.data_ptr(), codebook.shape[0],
                                       index.data_ptr() if M else None, dist.data_ptr() if M else None, stream)
@@ -90,7 +90,7 @@ def vq_update_centroids(vectors: Tensor, weights: Tensor, index: Tensor, codeboo
     if M == 0:
         return sums.zero_()
     stride = vectors.stride(0) if M > 1 else D
-    stream = torch.cuda.current_stream(vectors.device).cuda_stream
+    stream = _marshal.stream(vectors.device)
     with torch.cuda.device(vectors.device):
         rc = _lib.load().rf_vq_centroids(vectors.data_ptr(), stride, D, weights.data_ptr(), order.data_ptr(), offsets.data_ptr(), num_codes,
                                          codebook.data_ptr(), sums.data_ptr(), stream)

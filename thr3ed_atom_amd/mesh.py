@@ -14,7 +14,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _marshal
 
 MAX_SUBDIVISIONS = 8
 
@@ -38,7 +38,7 @@ def extract_mesh(voxel_grid, iso_level: float, subdivisions: int = 1, colours: b
     with torch.no_grad():
         grid = voxel_grid.to_rf_grid()  # (waits for parameters still arriving, like a render)
         dev = voxel_grid.kernel_tensors()[0].device
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _marshal.stream(dev)
         tiles = lib.rf_mesh_tiles(C.byref(grid), m)
         if tiles < 0:
             _lib.check(int(tiles), "rf_mesh_tiles")
@@ -57,7 +57,7 @@ def extract_mesh(voxel_grid, iso_level: float, subdivisions: int = 1, colours: b
         if num_vertices or num_faces:
             _lib.check(
                 lib.rf_mesh_emit(C.byref(grid), m, iso, offsets.data_ptr(), num_vertices, num_faces, keys.data_ptr(), vertices.data_ptr(),
-                                 None if cols is None else cols.data_ptr(), None if nrms is None else nrms.data_ptr(), face_edges.data_ptr(), stream),
+                                 _marshal.ptr(cols), _marshal.ptr(nrms), face_edges.data_ptr(), stream),
                 "rf_mesh_emit",
             )
         # the vertices come out in ascending edge key: a face's vertex index is the position of its edge key

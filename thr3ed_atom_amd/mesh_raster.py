@@ -16,10 +16,12 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _marshal
+from ._marshal import ptr
 from .camera import CameraIntrinsics, CameraPose, mse2psnr
 from .constants import EXTRA_ACCUMULATED_WEIGHTS
 from .mesh import Mesh
+from .metrics import ssim
 from .texture import TextureBake
 
 MAX_EDGE = _lib.RASTER_MAX_EDGE
@@ -34,17 +36,7 @@ class MeshRender(NamedTuple):
 
 
 def _check_raster_mesh(mesh: Mesh, bake: Optional[TextureBake]):
-    vertices, faces = mesh.vertices, mesh.faces
-    if not (torch.is_tensor(vertices) and torch.is_tensor(faces)):
-        raise ValueError("render_mesh takes a Mesh of tensors")
-    if not vertices.is_cuda or not faces.is_cuda:
-        raise ValueError(f"render_mesh takes a mesh on a HIP device (got vertices on {vertices.device}, faces on {faces.device}); there is no CPU path")
-    if vertices.device != faces.device:
-        raise ValueError(f"vertices are on {vertices.device}, faces on {faces.device}")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError("vertices must be a float32 tensor of shape [V, 3]")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int64, torch.int32):
-        raise ValueError("faces must be an integer tensor of shape [T, 3]")
+    vertices, faces = _marshal.mesh_arrays(mesh, "render_mesh")
     dev, V, T = vertices.device, vertices.shape[0], faces.shape[0]
     uvs = texture = colours = None
     if bake is not None:
@@ -65,22 +57,10 @@ def _check_raster_mesh(mesh: Mesh, bake: Optional[TextureBake]):
         if tuple(colours.shape) != (V, 3) or colours.dtype != torch.float32:
             raise ValueError("colours must be a float32 tensor of shape [V, 3]")
         colours = colours.detach().contiguous()
-    return vertices.detach().contiguous(), faces.detach().to(torch.int64).contiguous(), uvs, texture, colours
+    return vertices, faces, uvs, texture, colours
 
 
-def _camera(camera_pose: CameraPose, camera_intrinsics: CameraIntrinsics) -> "_lib.RFCamera":
-    from .ops import _camera_struct
-
-    height, width, focal = camera_intrinsics
-    if isinstance(height, bool) or isinstance(width, bool) or int(height) != height or int(width) != width or not (1 <= int(height) <= MAX_EDGE and 1 <= int(width) <= MAX_EDGE):
-        raise ValueError(f"the image must be between 1 and {MAX_EDGE} pixels along each edge, got {height} x {width}")
-    focal = float(np.float32(focal))
-    if not (math.isfinite(focal) and focal > 0.0):
-        raise ValueError(f"focal must be positive and finite, got {camera_intrinsics[2]!r}")
-    cam = _camera_struct(height, width, focal, camera_pose.rotation, camera_pose.translation)
-    if not all(math.isfinite(x) for x in cam.pose):
-        raise ValueError("the camera pose is not finite")
-    return cam
+_camera = _marshal.checked_camera
 
 
 def render_mesh(mesh: Mesh, camera_pose: CameraPose, camera_intrinsics: CameraIntrinsics, bake: Optional[TextureBake] = None, *, near: float = 0.0,
@@ -102,9 +82,7 @@ def render_mesh(mesh: Mesh, camera_pose: CameraPose, camera_intrinsics: CameraIn
     negative, a pose that is not finite."""
     vertices, faces, uvs, texture, colours = _check_raster_mesh(mesh, bake)
     cam = _camera(camera_pose, camera_intrinsics)
-    near = float(np.float32(near))
-    if not (math.isfinite(near) and near >= 0.0):
-        raise ValueError(f"near must be non-negative and finite, got {near!r}")
+    near = _marshal.non_negative(near, "near")
     H, W, T, V, dev = cam.height, cam.width, faces.shape[0], vertices.shape[0], vertices.device
     background = 1.0 if white_bkgd else 0.0
     has_colour = texture is not None or colours is not None
@@ -114,21 +92,18 @@ def render_mesh(mesh: Mesh, camera_pose: CameraPose, camera_intrinsics: CameraIn
                           torch.full((H, W), -1, dtype=torch.int32, device=dev), torch.zeros((H, W, 3), dtype=torch.float32, device=dev) if barycentrics else None)
     lib = _lib.load()
     with torch.no_grad():
-        if not bool(torch.isfinite(vertices).all()):
-            raise ValueError("the mesh has vertices that are not finite")
+        _marshal.require_finite_vertices(vertices)
         flags = (_lib.FLAG_WHITE_BKGD if white_bkgd else 0) | (_lib.RASTER_CULL_BACKFACES if cull_backfaces else 0)
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _marshal.stream(dev)
         visibility = torch.full((H, W), -1, dtype=torch.int64, device=dev)  # all ones: nothing hit
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         rc = lib.rf_mesh_raster_visibility(C.byref(cam), vertices.data_ptr(), V, faces.data_ptr(), T, near, flags, visibility.data_ptr(), status.data_ptr(), stream)
         _lib.check(rc, "rf_mesh_raster_visibility")
-        if int(status.item()):
-            raise ValueError(f"faces index outside [0, {V})")
+        _marshal.require_faces_in_range(status, V)
         colour = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if has_colour else None
         depth = torch.empty((H, W, 1), dtype=torch.float32, device=dev)
         face_ids = torch.empty((H, W), dtype=torch.int32, device=dev)
         bary = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if barycentrics else None
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         th, tw = (0, 0) if texture is None else (texture.shape[0], texture.shape[1])
         rc = lib.rf_mesh_raster_shade(C.byref(cam), vertices.data_ptr(), V, faces.data_ptr(), T, visibility.data_ptr(), ptr(uvs), ptr(texture), th, tw,
                                       ptr(colours), flags, ptr(colour), depth.data_ptr(), face_ids.data_ptr(), ptr(bary), stream)
@@ -144,8 +119,6 @@ def evaluate_mesh_against_field(mesh: Mesh, bake: Optional[TextureBake], vol_mod
     "same" for images below 11 pixels) of the colours, ``depth_l1`` (mean |mesh depth - median depth| over the pixels both cover;
     NaN for a view without any) and ``mask_iou`` (mesh mask against accumulated weight > 1/2; 1 when both are empty), and
     ``per_image``: the list of the same four numbers per view.  Views whose ``depth_l1`` is NaN do not enter its mean."""
-    from .metrics import ssim
-
     cfg = getattr(vol_mod, "render_config", None)
     white = bool(render_overrides.get("white_bkgd", getattr(cfg, "white_bkgd", False)))
     height, width, _ = camera_intrinsics

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib, ops
+from . import _lib, _marshal, ops
 from .mesh import Mesh
 
 MAX_TARGET_RESOLUTION = 4096  # target_faces: the largest number of cells along the longest axis that the bisection tries
@@ -41,22 +41,14 @@ class _Lattice(NamedTuple):
 
 
 def _check_mesh(mesh: Mesh):
-    vertices, faces = mesh.vertices, mesh.faces
-    if not (torch.is_tensor(vertices) and torch.is_tensor(faces)):
-        raise ValueError("simplify_mesh takes a Mesh of tensors")
-    if not vertices.is_cuda or not faces.is_cuda:
-        raise ValueError(f"simplify_mesh takes a mesh on a HIP device (got vertices on {vertices.device}, faces on {faces.device}); there is no CPU path")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError("vertices must be a float32 tensor of shape [V, 3]")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int64, torch.int32):
-        raise ValueError("faces must be an integer tensor of shape [T, 3]")
+    vertices, faces = _marshal.mesh_arrays(mesh, "simplify_mesh")
     if vertices.shape[0] >= 2**31:
         raise ValueError("simplify_mesh takes fewer than 2^31 vertices")
     for name, t in (("colours", mesh.colours), ("normals", mesh.normals)):
         if t is not None and (not torch.is_tensor(t) or t.device != vertices.device or t.dtype != torch.float32 or tuple(t.shape) != tuple(vertices.shape)):
             raise ValueError(f"{name} must be a float32 tensor of the vertices' shape on their device")
     contiguous = lambda t: None if t is None else t.detach().contiguous()
-    return Mesh(contiguous(vertices), contiguous(faces.to(torch.int64)), contiguous(mesh.colours), contiguous(mesh.normals))
+    return Mesh(vertices, faces, contiguous(mesh.colours), contiguous(mesh.normals))
 
 
 def cell_size_for(extent, resolution: int) -> np.float32:

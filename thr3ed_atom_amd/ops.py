@@ -16,7 +16,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _marshal
 from .voxels import VoxelGrid, as_kernel_grid
 
 _T_VALS_CACHE: Dict[Tuple[int, str], Tensor] = {}
@@ -134,13 +134,7 @@ def _list_label(grid: "VoxelGrid", render_diffuse) -> str:
     return "diffuse" if render_diffuse or grid.sh_degree == 0 else "sh" + str(grid.sh_degree)
 
 
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _require_hip(t: Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must live on a HIP device (got {t.device}); the render path has no CPU fallback")
+_ptr, _stream, _require_hip, _camera_struct = _marshal.ptr, _marshal.stream, _marshal.require_hip, _marshal.camera_struct
 
 
 def t_vals_for(num_samples: int, device) -> Tensor:
@@ -152,10 +146,6 @@ def t_vals_for(num_samples: int, device) -> Tensor:
         t = torch.linspace(0.0, 1.0, int(num_samples), dtype=torch.float32).to(device)
         _T_VALS_CACHE[key] = t
     return t
-
-
-def _ptr(t: Optional[Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 class KeyedJitter(NamedTuple):
@@ -194,6 +184,46 @@ def _ray_batch(origins: Tensor, directions: Tensor, num_samples: int, near: floa
     return rb, tv
 
 
+class RayBatch(NamedTuple):
+    """The rays of one launch: a ray list (``origins`` / ``directions`` [N, 3]) or, with ``camera`` =
+    (height, width, focal, rotation [3,3], translation [3]), pixels [first_ray, first_ray + num_rays) of a posed pinhole camera
+    generated inside the kernel (default: the whole frame).  ``t_rand``: None, a [N, S] tensor or a KeyedJitter."""
+
+    origins: Optional[Tensor]
+    directions: Optional[Tensor]
+    num_samples: int
+    near: float
+    far: float
+    t_rand: object = None
+    camera: Optional[tuple] = None
+    first_ray: int = 0
+    num_rays: Optional[int] = None
+
+
+def _ray_batch_struct(rays: RayBatch, dev, what: str):
+    """The RFRayBatch of a RayBatch and what must stay alive until the launch is enqueued (the camera struct, t_vals)."""
+    if rays.camera is not None:
+        cam = _camera_struct(*rays.camera)
+        rb = _lib.RFRayBatch()
+        rb.num_rays = cam.height * cam.width - int(rays.first_ray) if rays.num_rays is None else int(rays.num_rays)
+        rb.num_samples, rb.near, rb.far = int(rays.num_samples), rays.near, rays.far
+        tv = t_vals_for(rays.num_samples, dev)
+        rb.t_vals_dev = tv.data_ptr()
+        rb.first_ray = int(rays.first_ray)
+        rb.camera = C.pointer(cam)
+        if isinstance(rays.t_rand, KeyedJitter):
+            rb.jitter_key = int(rays.t_rand.key) & 0xFFFFFFFFFFFFFFFF
+        elif rays.t_rand is not None:
+            rb.t_rand_dev = rays.t_rand.data_ptr()
+        return rb, (cam, tv)
+    for name, t in (("ray origins", rays.origins), ("ray directions", rays.directions)):
+        _require_hip(t, name)
+        if not (t.is_contiguous() and t.dtype == torch.float32):
+            raise ValueError(f"{what} takes contiguous float32 rays")
+    rb, tv = _ray_batch(rays.origins, rays.directions, rays.num_samples, rays.near, rays.far, rays.t_rand)
+    return rb, (tv,)
+
+
 def _fill_caches(out, caches):
     """the sample cache of a saving forward render (sample_cache, trans_cache, stop, chunk_mask) into an RFRenderOut"""
     out.sample_cache_dev, out.trans_cache_dev, out.stop_cache_dev, out.chunk_mask_dev = (t.data_ptr() for t in caches)
@@ -220,6 +250,17 @@ def _render_out(n: int, num_samples: int, dev, save: bool, key_hist: Optional[Te
         if key_hist is not None:
             out.key_hist_dev, out.brick_size = key_hist.data_ptr(), int(brick_size)
     return (colour, depth, acc, disparity), caches, out
+
+
+def _adjoint_args(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_rand, num_samples: int, near: float, far: float, flags: int, caches, g_colour, g_depth,
+                  g_acc, as_forward: bool = False):
+    """The leading arguments every adjoint entry point takes -- (grid, rays, flags, fwd, grads): the grid in the layout of its
+    Parameters (``as_forward``: as the forward pass read it), the rays of the forward render, its caches and the upstream
+    gradients -- and what must stay alive until the launch is enqueued."""
+    rf_grid = (grid.forward_rf_grid if as_forward else grid.to_rf_grid)(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
+    rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
+    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
+    return (C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads)), (rb, tv, fwd, grads)
 
 
 def render_forward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_rand: Optional[Tensor], num_samples: int,
@@ -253,28 +294,13 @@ def render_frame_raw(grid: VoxelGrid, height: int, width: int, focal: float, rot
     first, _ = grid.kernel_tensors()
     dev = first.device
     _require_hip(first, "grid tensor")
-    n = int(height) * int(width) - int(first_ray) if num_rays is None else int(num_rays)
-    cam = _lib.RFCamera()
-    cam.height, cam.width, cam.focal = int(height), int(width), float(np.float32(focal))
-    rot = torch.as_tensor(rotation).detach().to("cpu", torch.float32).reshape(3, 3)
-    trans = torch.as_tensor(translation).detach().to("cpu", torch.float32).reshape(3)
-    for i in range(3):
-        for j in range(3):
-            cam.pose[4 * i + j] = float(rot[i, j])
-        cam.pose[4 * i + 3] = float(trans[i])
-    rb = _lib.RFRayBatch()
-    rb.num_rays, rb.num_samples, rb.near, rb.far = n, int(num_samples), near, far
-    tv = t_vals_for(num_samples, dev)
-    rb.t_vals_dev = tv.data_ptr()
-    rb.first_ray = int(first_ray)
-    rb.camera = C.pointer(cam)
-    if jitter is not None:
-        rb.jitter_key = int(jitter.key) & 0xFFFFFFFFFFFFFFFF
-        flags = int(flags) | _lib.FLAG_JITTER_KEYED
+    rays = RayBatch(None, None, num_samples, near, far, t_rand=jitter, camera=(height, width, focal, rotation, translation), first_ray=first_ray, num_rays=num_rays)
+    rb, keep = _ray_batch_struct(rays, dev, "rf_render_forward")
     rf_grid = grid.forward_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
-    tensors, _, out = _render_out(n, num_samples, dev, save=False)
+    tensors, _, out = _render_out(int(rb.num_rays), num_samples, dev, save=False)
     with _span(f"render_forward[{_variant(grid, flags)},frame]", dev):
-        rc = lib.rf_render_forward(C.byref(rf_grid), C.byref(rb), int(flags), C.byref(out), _stream(dev))
+        rc = lib.rf_render_forward(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, jitter), C.byref(out), _stream(dev))
+    del keep
     _lib.check(rc, "rf_render_forward")
     return tensors
 
@@ -286,13 +312,9 @@ def render_backward_raw(grid: VoxelGrid, origins: Tensor, directions: Tensor, t_
     order of grid.kernel_tensors())."""
     lib = _lib.load()
     dev = origins.device
-    rf_grid = grid.to_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
-    rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
+    args, keep = _adjoint_args(grid, origins, directions, t_rand, num_samples, near, far, flags, caches, g_colour, g_depth, g_acc)
     with _span(f"render_backward[{_variant(grid, flags)}]", dev):
-        rc = lib.rf_render_backward(
-            C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), grad_first.data_ptr(), _ptr(grad_second), _stream(dev)
-        )
+        rc = lib.rf_render_backward(*args, grad_first.data_ptr(), _ptr(grad_second), _stream(dev))
     _lib.check(rc, "rf_render_backward")
 
 
@@ -304,13 +326,11 @@ def render_backward_rays_raw(grid: VoxelGrid, origins: Tensor, directions: Tenso
     lib = _lib.load()
     dev = origins.device
     n = origins.shape[0]
-    rf_grid = grid.forward_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
-    rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
+    args, keep = _adjoint_args(grid, origins, directions, t_rand, num_samples, near, far, flags, caches, g_colour, g_depth, g_acc, as_forward=True)
     go = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_origins else None
     gdir = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_directions else None
     with _span(f"render_backward_rays[{_variant(grid, flags)}]", dev):
-        rc = lib.rf_render_backward_rays(C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), _ptr(go), _ptr(gdir), _stream(dev))
+        rc = lib.rf_render_backward_rays(*args, _ptr(go), _ptr(gdir), _stream(dev))
     _lib.check(rc, "rf_render_backward_rays")
     return go, gdir
 
@@ -337,14 +357,9 @@ def render_backward_emit_raw(grid: VoxelGrid, origins: Tensor, directions: Tenso
     ``hist`` (int32 [8 * num_bricks], optional) is incremented by the number of records per key (for ``bin_records_by_brick``)."""
     lib = _lib.load()
     dev = origins.device
-    rf_grid = grid.to_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
-    rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
+    args, keep = _adjoint_args(grid, origins, directions, t_rand, num_samples, near, far, flags, caches, g_colour, g_depth, g_acc)
     with _span(f"render_backward_emit[{_variant(grid, flags)}]", dev):
-        rc = lib.rf_render_backward_emit(
-            C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), int(brick_size), keys.data_ptr(), records.data_ptr(),
-            _ptr(hist), _stream(dev),
-        )
+        rc = lib.rf_render_backward_emit(*args, int(brick_size), keys.data_ptr(), records.data_ptr(), _ptr(hist), _stream(dev))
     _lib.check(rc, "rf_render_backward_emit")
 
 
@@ -356,14 +371,9 @@ def render_backward_emit_direct_raw(grid: VoxelGrid, origins: Tensor, directions
     then ``bin_offsets``) write their expanded records straight to their final positions in ``records_sorted``."""
     lib = _lib.load()
     dev = origins.device
-    rf_grid = grid.to_rf_grid(use_occupancy=bool(flags & _lib.FLAG_OCCUPANCY_SKIP))
-    rb, tv = _ray_batch(origins, directions, num_samples, near, far, t_rand)
-    grads, fwd = _render_grads(g_colour, g_depth, g_acc), _fill_caches(_lib.RFRenderOut(), caches)
+    args, keep = _adjoint_args(grid, origins, directions, t_rand, num_samples, near, far, flags, caches, g_colour, g_depth, g_acc)
     with _span(f"render_backward_emit_direct[{_variant(grid, flags)}]", dev):
-        rc = lib.rf_render_backward_emit_direct(
-            C.byref(rf_grid), C.byref(rb), _jitter_flags(flags, t_rand), C.byref(fwd), C.byref(grads), int(brick_size), cursor.data_ptr(),
-            records_sorted.data_ptr(), _ptr(hist_clear), _stream(dev),
-        )
+        rc = lib.rf_render_backward_emit_direct(*args, int(brick_size), cursor.data_ptr(), records_sorted.data_ptr(), _ptr(hist_clear), _stream(dev))
     _lib.check(rc, "rf_render_backward_emit_direct")
 
 
@@ -1053,62 +1063,10 @@ def total_variation(grid: VoxelGrid, epsilon: float = 1e-8) -> Tuple[Tensor, Ten
     return _TotalVariation.apply(first, second, grid, float(epsilon))
 
 
-class RayBatch(NamedTuple):
-    """The rays of one rf_node_max_weight launch: a ray list (``origins`` / ``directions`` [N, 3]) or, with ``camera`` =
-    (height, width, focal, rotation [3,3], translation [3]), pixels [first_ray, first_ray + num_rays) of a posed pinhole camera
-    generated inside the kernel (default: the whole frame).  ``t_rand``: None, a [N, S] tensor or a KeyedJitter."""
-
-    origins: Optional[Tensor]
-    directions: Optional[Tensor]
-    num_samples: int
-    near: float
-    far: float
-    t_rand: object = None
-    camera: Optional[tuple] = None
-    first_ray: int = 0
-    num_rays: Optional[int] = None
-
-
-def _camera_struct(height, width, focal, rotation, translation) -> "_lib.RFCamera":
-    cam = _lib.RFCamera()
-    cam.height, cam.width, cam.focal = int(height), int(width), float(np.float32(focal))
-    rot = torch.as_tensor(rotation).detach().to("cpu", torch.float32).reshape(3, 3)
-    trans = torch.as_tensor(translation).detach().to("cpu", torch.float32).reshape(3)
-    for i in range(3):
-        for j in range(3):
-            cam.pose[4 * i + j] = float(rot[i, j])
-        cam.pose[4 * i + 3] = float(trans[i])
-    return cam
-
-
 def _check_node_buffer(grid: VoxelGrid, t: Tensor, dtype, name: str) -> None:
     _require_hip(t, name)
     if tuple(t.shape) != tuple(grid.grid_dims) or t.dtype != dtype or not t.is_contiguous():
         raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(grid.grid_dims)} (plain node order), got {t.dtype} {tuple(t.shape)}")
-
-
-def _ray_batch_struct(rays: RayBatch, dev, what: str):
-    """The RFRayBatch of a RayBatch and what must stay alive until the launch is enqueued (the camera struct, t_vals)."""
-    if rays.camera is not None:
-        cam = _camera_struct(*rays.camera)
-        rb = _lib.RFRayBatch()
-        rb.num_rays = cam.height * cam.width - int(rays.first_ray) if rays.num_rays is None else int(rays.num_rays)
-        rb.num_samples, rb.near, rb.far = int(rays.num_samples), rays.near, rays.far
-        tv = t_vals_for(rays.num_samples, dev)
-        rb.t_vals_dev = tv.data_ptr()
-        rb.first_ray = int(rays.first_ray)
-        rb.camera = C.pointer(cam)
-        if isinstance(rays.t_rand, KeyedJitter):
-            rb.jitter_key = int(rays.t_rand.key) & 0xFFFFFFFFFFFFFFFF
-        elif rays.t_rand is not None:
-            rb.t_rand_dev = rays.t_rand.data_ptr()
-        return rb, (cam, tv)
-    for name, t in (("ray origins", rays.origins), ("ray directions", rays.directions)):
-        _require_hip(t, name)
-        if not (t.is_contiguous() and t.dtype == torch.float32):
-            raise ValueError(f"{what} takes contiguous float32 rays")
-    rb, tv = _ray_batch(rays.origins, rays.directions, rays.num_samples, rays.near, rays.far, rays.t_rand)
-    return rb, (tv,)
 
 
 def node_max_weight_raw(grid: VoxelGrid, rays: RayBatch, flags: int, out: Tensor) -> None:
@@ -1193,6 +1151,27 @@ class _DistortionLoss(torch.autograd.Function):
         return ret, None, None, None
 
 
+def _flat_ray_batch(rays, num_samples: int, bounds, perturb: bool, t_rand, jitter_key: Optional[int], what: str) -> RayBatch:
+    """The RayBatch of flat ``rays`` (detached, float32, contiguous) between ``bounds`` (a CameraBounds or (near, far)) with the jitter
+    ``distortion_loss`` documents: ``t_rand`` (a [N, S] tensor or a KeyedJitter), else ``jitter_key``, else with ``perturb`` a freshly
+    drawn key, else none."""
+    near, far = (bounds.near, bounds.far) if hasattr(bounds, "near") else bounds
+    origins = rays.origins.detach().to(torch.float32).contiguous()
+    directions = rays.directions.detach().to(torch.float32).contiguous()
+    if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
+        raise AssertionError(f"{what} takes FLAT rays [N, 3]")
+    if t_rand is None:
+        if jitter_key is not None:
+            t_rand = KeyedJitter(int(jitter_key), 0)
+        elif perturb:
+            t_rand = KeyedJitter(draw_jitter_key(), 0)
+    elif not isinstance(t_rand, KeyedJitter):
+        t_rand = t_rand.detach().to(origins.device, torch.float32).contiguous()
+        if tuple(t_rand.shape) != (origins.shape[0], int(num_samples)):
+            raise ValueError(f"t_rand must be [{origins.shape[0]}, {int(num_samples)}]")
+    return RayBatch(origins, directions, int(num_samples), float(np.float32(near)), float(np.float32(far)), t_rand=t_rand)
+
+
 def distortion_loss(grid_or_model, rays, num_samples: int, bounds, *, perturb: bool = False, t_rand=None, jitter_key: Optional[int] = None,
                     optimized_sampling: bool = False, use_occupancy: bool = False) -> Tensor:
     """The distortion loss of mip-NeRF 360 on the compositing weights of ``rays`` (a Rays-like object with flat ``origins`` /
@@ -1208,23 +1187,9 @@ def distortion_loss(grid_or_model, rays, num_samples: int, bounds, *, perturb: b
     one backward; the backward adds into the grid's gradient bucket (optim.FlatGrid) when it has one.  The gradient reaches the raw
     densities only: none goes to the features, and none to rays or poses (``rays`` are used detached)."""
     grid = as_kernel_grid(getattr(grid_or_model, "thre3d_repr", grid_or_model))
-    near, far = (bounds.near, bounds.far) if hasattr(bounds, "near") else bounds
-    origins = rays.origins.detach().to(torch.float32).contiguous()
-    directions = rays.directions.detach().to(torch.float32).contiguous()
-    if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
-        raise AssertionError("distortion_loss takes FLAT rays [N, 3]")
-    if t_rand is None:
-        if jitter_key is not None:
-            t_rand = KeyedJitter(int(jitter_key), 0)
-        elif perturb:
-            t_rand = KeyedJitter(draw_jitter_key(), 0)
-    elif not isinstance(t_rand, KeyedJitter):
-        t_rand = t_rand.detach().to(origins.device, torch.float32).contiguous()
-        if tuple(t_rand.shape) != (origins.shape[0], int(num_samples)):
-            raise ValueError(f"t_rand must be [{origins.shape[0]}, {int(num_samples)}]")
+    batch = _flat_ray_batch(rays, num_samples, bounds, perturb, t_rand, jitter_key, "distortion_loss")
     if use_occupancy and not grid.occupancy_current():
         grid.build_occupancy()
-    batch = RayBatch(origins, directions, int(num_samples), float(np.float32(near)), float(np.float32(far)), t_rand=t_rand)
     first, _ = grid.kernel_tensors()
     return _DistortionLoss.apply(first, grid, batch, render_flags(False, False, optimized_sampling, use_occupancy))
 
@@ -1296,25 +1261,12 @@ def render_geometry(grid_or_model, rays, num_samples: int, bounds, *, quantile: 
     reference VoxelGrid's attribute names.  Runs under no_grad: the outputs carry NO gradient, neither to the grid nor to the rays."""
     quantile = _check_quantile(quantile)
     grid = as_kernel_grid(getattr(grid_or_model, "thre3d_repr", grid_or_model))
-    near, far = (bounds.near, bounds.far) if hasattr(bounds, "near") else bounds
-    origins = rays.origins.detach().to(torch.float32).contiguous()
-    directions = rays.directions.detach().to(torch.float32).contiguous()
-    if origins.dim() != 2 or origins.shape != directions.shape or origins.shape[-1] != 3:
-        raise AssertionError("render_geometry takes FLAT rays [N, 3]")
-    if t_rand is None:
-        if jitter_key is not None:
-            t_rand = KeyedJitter(int(jitter_key), 0)
-        elif perturb:
-            t_rand = KeyedJitter(draw_jitter_key(), 0)
-    elif not isinstance(t_rand, KeyedJitter):
-        t_rand = t_rand.detach().to(origins.device, torch.float32).contiguous()
-        if tuple(t_rand.shape) != (origins.shape[0], int(num_samples)):
-            raise ValueError(f"t_rand must be [{origins.shape[0]}, {int(num_samples)}]")
+    batch = _flat_ray_batch(rays, num_samples, bounds, perturb, t_rand, jitter_key, "render_geometry")
     _require_hip(grid.kernel_tensors()[0], "grid tensor")
     if use_occupancy_mask and not grid.occupancy_current():
         grid.build_occupancy()
-    batch = RayBatch(origins, directions, int(num_samples), float(np.float32(near)), float(np.float32(far)), t_rand=t_rand)
-    return _geometry_render_out(grid, [(0, batch, origins.shape[0])], origins.shape[0], render_flags(False, False, optimized_sampling, use_occupancy_mask), quantile)
+    n = batch.origins.shape[0]
+    return _geometry_render_out(grid, [(0, batch, n)], n, render_flags(False, False, optimized_sampling, use_occupancy_mask), quantile)
 
 
 def render_geometry_frame(grid, camera_intrinsics, camera_pose, render_config, quantile: float = 0.5, chunk_size: Optional[int] = None):

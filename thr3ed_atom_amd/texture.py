@@ -25,8 +25,10 @@ import numpy as np
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _marshal
+from ._marshal import checked_camera, mesh_arrays, non_negative, ptr, require_faces_in_range, require_finite_vertices
 from .camera import CameraPose
+from .constants import EXTRA_ACCUMULATED_WEIGHTS
 from .mesh import Mesh, to8b
 from .voxels import as_kernel_grid
 
@@ -101,21 +103,6 @@ def corner_uvs(layout: AtlasLayout, num_faces: int) -> np.ndarray:
     return np.stack([u, v], axis=-1).astype(np.float32)
 
 
-def _check_bake_mesh(mesh: Mesh):
-    vertices, faces = mesh.vertices, mesh.faces
-    if not (torch.is_tensor(vertices) and torch.is_tensor(faces)):
-        raise ValueError("bake_texture takes a Mesh of tensors")
-    if not vertices.is_cuda or not faces.is_cuda:
-        raise ValueError(f"bake_texture takes a mesh on a HIP device (got vertices on {vertices.device}, faces on {faces.device}); there is no CPU path")
-    if vertices.device != faces.device:
-        raise ValueError(f"vertices are on {vertices.device}, faces on {faces.device}")
-    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError("vertices must be a float32 tensor of shape [V, 3]")
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int64, torch.int32):
-        raise ValueError("faces must be an integer tensor of shape [T, 3]")
-    return vertices.detach().contiguous(), faces.detach().to(torch.int64).contiguous()
-
-
 def bake_texture(mesh: Mesh, grid_or_model, patch: int = 8, *, reach: Optional[float] = None, samples: int = 16, diffuse: bool = False,
                  cols: Optional[int] = None, opacity: bool = True) -> TextureBake:
     """Bake the appearance of a field onto ``mesh`` (vertices float32 [V, 3], faces [T, 3], on the field's HIP device) as a
@@ -133,7 +120,7 @@ def bake_texture(mesh: Mesh, grid_or_model, patch: int = 8, *, reach: Optional[f
     ValueError: a CPU mesh or grid, mesh and grid on different devices, non-finite vertices, faces indexing outside the vertices,
     patch outside [2, 64], samples outside [1, 256], a negative or non-finite reach, cols too small for the faces' blocks to stay
     within 16384 texels per edge."""
-    vertices, faces = _check_bake_mesh(mesh)
+    vertices, faces = mesh_arrays(mesh, "bake_texture")
     grid = as_kernel_grid(getattr(grid_or_model, "thre3d_repr", grid_or_model))
     first = grid.kernel_tensors()[0]
     if not first.is_cuda:
@@ -144,9 +131,7 @@ def bake_texture(mesh: Mesh, grid_or_model, patch: int = 8, *, reach: Optional[f
         raise ValueError(f"samples must be an integer in [1, {MAX_SAMPLES}], got {samples!r}")
     if reach is None:
         reach = 2.0 * max((hi - lo) / n for (lo, hi), n in zip(grid.aabb, grid.grid_dims))
-    reach = float(np.float32(reach))
-    if not (math.isfinite(reach) and reach >= 0.0):
-        raise ValueError(f"reach must be non-negative and finite, got {reach!r}")
+    reach = non_negative(reach, "reach")
     T, V, dev = faces.shape[0], vertices.shape[0], vertices.device
     layout = atlas_layout(T, patch, cols)
     uvs = torch.from_numpy(corner_uvs(layout, T)).to(dev)
@@ -155,42 +140,29 @@ def bake_texture(mesh: Mesh, grid_or_model, patch: int = 8, *, reach: Optional[f
                            uvs, layout.patch, layout.block, layout.cols, layout.rows)
     lib = _lib.load()
     with torch.no_grad():
-        if not bool(torch.isfinite(vertices).all()):
-            raise ValueError("the mesh has vertices that are not finite")
+        require_finite_vertices(vertices)
         texture = torch.empty((layout.height, layout.width, 3), dtype=torch.float32, device=dev)
         alpha = torch.empty((layout.height, layout.width), dtype=torch.float32, device=dev) if opacity else None
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         rf_grid = grid.to_rf_grid()  # (waits for parameters still arriving, like a render)
         flags = _lib.FLAG_RENDER_DIFFUSE if diffuse else 0
         rc = lib.rf_texture_bake(C.byref(rf_grid), vertices.data_ptr(), V, faces.data_ptr(), T, layout.patch, layout.cols, layout.rows, reach, int(samples),
-                                 flags, texture.data_ptr(), None if alpha is None else alpha.data_ptr(), status.data_ptr(),
-                                 torch.cuda.current_stream(dev).cuda_stream)
+                                 flags, texture.data_ptr(), ptr(alpha), status.data_ptr(), _marshal.stream(dev))
         _lib.check(rc, "rf_texture_bake")
-        if int(status.item()):
-            raise ValueError(f"faces index outside [0, {V})")
+        require_faces_in_range(status, V)
     return TextureBake(texture, alpha, uvs, layout.patch, layout.block, layout.cols, layout.rows)
-
-
-def _non_negative(value, name: str) -> float:
-    value = float(np.float32(value))
-    if not (math.isfinite(value) and value >= 0.0):
-        raise ValueError(f"{name} must be non-negative and finite, got {value!r}")
-    return value
 
 
 class _ViewProjector:
     """The state of one view bake: the checked mesh, the atlas, the accumulators; ``add`` takes at most 16 views at a time."""
 
     def __init__(self, mesh: Mesh, camera_intrinsics, patch, cols, near, depth_bias, min_cos, cos_power, two_sided, background):
-        from .mesh_raster import _camera  # (mesh_raster imports this module)
-
-        self._camera = _camera
-        self.vertices, self.faces = _check_bake_mesh(mesh)
+        self.vertices, self.faces = mesh_arrays(mesh, "bake_texture")  # (the view bakes report the mesh in bake_texture's words)
         self.intrinsics = camera_intrinsics
         self.H, self.W = int(camera_intrinsics[0]), int(camera_intrinsics[1])
         self.T, self.V, self.dev = self.faces.shape[0], self.vertices.shape[0], self.vertices.device
         self.layout = atlas_layout(self.T, patch, cols)
-        self.near, self.background = _non_negative(near, "near"), _non_negative(background, "background")
+        self.near, self.background = non_negative(near, "near"), non_negative(background, "background")
         min_cos = float(np.float32(min_cos))
         if not 0.0 <= min_cos < 1.0:
             raise ValueError(f"min_cos must be in [0, 1), got {min_cos!r}")
@@ -201,8 +173,7 @@ class _ViewProjector:
         self.accum = self.count = self.visibility = self.status = None
         with torch.no_grad():
             if self.T:
-                if not bool(torch.isfinite(self.vertices).all()):
-                    raise ValueError("the mesh has vertices that are not finite")
+                require_finite_vertices(self.vertices)
                 if int(self.faces.min()) < 0 or int(self.faces.max()) >= self.V:
                     raise ValueError(f"faces index outside [0, {self.V})")
                 if depth_bias is None:  # the mean edge length of the faces
@@ -211,8 +182,8 @@ class _ViewProjector:
                 self.accum = torch.zeros((self.layout.height, self.layout.width, 4), dtype=torch.float32, device=self.dev)
                 self.count = torch.zeros((self.layout.height, self.layout.width), dtype=torch.int32, device=self.dev)
                 self.status = torch.zeros(1, dtype=torch.int32, device=self.dev)
-        self.depth_bias = _non_negative(0.0 if depth_bias is None else depth_bias, "depth_bias")
-        self._camera(CameraPose(torch.eye(3), torch.zeros(3, 1)), camera_intrinsics)  # (the intrinsics' own errors, even with zero views)
+        self.depth_bias = non_negative(0.0 if depth_bias is None else depth_bias, "depth_bias")
+        checked_camera(CameraPose(torch.eye(3), torch.zeros(3, 1)), camera_intrinsics)  # (the intrinsics' own errors, even with zero views)
 
     def add(self, images: Tensor, poses, alphas: Optional[Tensor], intrinsics=None) -> None:
         n = len(poses)
@@ -225,14 +196,14 @@ class _ViewProjector:
             raise ValueError(f"the images of {n} views of {self.H} x {self.W} pixels must have shape {(n, self.H, self.W, 3)}, got {tuple(images.shape)}")
         if alphas is not None and tuple(alphas.shape) != (n, self.H, self.W):
             raise ValueError(f"the alphas of {n} views of {self.H} x {self.W} pixels must have shape {(n, self.H, self.W)}, got {tuple(alphas.shape)}")
-        cams = (_lib.RFCamera * n)(*[self._camera(pose, intr) for pose, intr in zip(poses, intrinsics)])
+        cams = (_lib.RFCamera * n)(*[checked_camera(pose, intr) for pose, intr in zip(poses, intrinsics)])
         if not self.T:
             return
         lib = _lib.load()
         with torch.no_grad():
             images = images.detach().to(self.dev, torch.float32).contiguous()
             alphas = None if alphas is None else alphas.detach().to(self.dev, torch.float32).contiguous()
-            stream = torch.cuda.current_stream(self.dev).cuda_stream
+            stream = _marshal.stream(self.dev)
             if self.visibility is None:
                 self.visibility = torch.empty((MAX_VIEWS, self.H, self.W), dtype=torch.int64, device=self.dev)
             self.visibility[:n].fill_(-1)  # all ones: nothing hit
@@ -241,7 +212,7 @@ class _ViewProjector:
                                                    self.visibility[k].data_ptr(), self.status.data_ptr(), stream)
                 _lib.check(rc, "rf_mesh_raster_visibility")
             rc = lib.rf_texture_project_views(self.vertices.data_ptr(), self.V, self.faces.data_ptr(), self.T, self.layout.patch, self.layout.cols, self.layout.rows,
-                                              n, cams, images.data_ptr(), self.visibility.data_ptr(), None if alphas is None else alphas.data_ptr(), self.near,
+                                              n, cams, images.data_ptr(), self.visibility.data_ptr(), ptr(alphas), self.near,
                                               self.depth_bias, self.min_cos, self.cos_power, self.background, self.flags, self.accum.data_ptr(),
                                               self.count.data_ptr(), self.status.data_ptr(), stream)
             _lib.check(rc, "rf_texture_project_views")
@@ -260,8 +231,7 @@ class _ViewProjector:
             empty = TextureBake(torch.empty((0, 0, 3), dtype=torch.float32, device=dev), None, uvs, lay.patch, lay.block, lay.cols, lay.rows)
             return ViewBake(empty, torch.empty((0, 0), dtype=torch.float32, device=dev), torch.empty((0, 0), dtype=torch.int32, device=dev))
         with torch.no_grad():
-            if int(self.status.item()):
-                raise ValueError(f"faces index outside [0, {self.V})")
+            require_faces_in_range(self.status, self.V)
             texture, weight = finalise_views(self.accum, None if fallback is None else fallback.texture.detach().to(torch.float32), min_weight)
         return ViewBake(TextureBake(texture, None, uvs, lay.patch, lay.block, lay.cols, lay.rows), weight, self.count)
 
@@ -322,7 +292,7 @@ def bake_texture_from_views(mesh: Mesh, images, poses: Sequence, camera_intrinsi
     if len(images) != N or (alphas is not None and len(alphas) != N):
         raise ValueError(f"{len(images)} images, {N} poses" + ("" if alphas is None else f", {len(alphas)} alphas") + ": the counts must match")
     intrinsics = _intrinsics_per_view(camera_intrinsics, N)
-    min_weight = _non_negative(min_weight, "min_weight")
+    min_weight = non_negative(min_weight, "min_weight")
     projector = _ViewProjector(mesh, intrinsics[0] if N else camera_intrinsics, patch, cols, near, depth_bias, min_cos, cos_power, two_sided, background)
     for lo in range(0, N, MAX_VIEWS):
         hi = min(lo + MAX_VIEWS, N)
@@ -340,12 +310,10 @@ def bake_texture_from_field_views(mesh: Mesh, vol_mod, poses: Sequence, camera_i
     ``render_overrides`` are passed on), the accumulated weight of ``vol_mod.render_geometry`` is the view's alpha plane -- the way
     ``evaluate_mesh_against_field`` obtains it -- and the model's background the background.  ``fallback`` defaults to
     ``bake_texture(mesh, vol_mod, patch)``; the other keywords are those of ``bake_texture_from_views``."""
-    from .constants import EXTRA_ACCUMULATED_WEIGHTS
-
     overrides = dict(render_overrides or {})
     cfg = getattr(vol_mod, "render_config", None)
     white = bool(overrides.get("white_bkgd", getattr(cfg, "white_bkgd", False)))
-    min_weight = _non_negative(min_weight, "min_weight")
+    min_weight = non_negative(min_weight, "min_weight")
     projector = _ViewProjector(mesh, camera_intrinsics, patch, kw.pop("cols", None), kw.pop("near", 0.0), kw.pop("depth_bias", None), kw.pop("min_cos", 0.1),
                                kw.pop("cos_power", 2), kw.pop("two_sided", False), 1.0 if white else 0.0)
     if kw:

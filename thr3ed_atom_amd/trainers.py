@@ -31,7 +31,7 @@ import torch
 from torch import Tensor
 from torch.nn.functional import mse_loss
 
-from . import _lib, ops
+from . import _lib, _marshal, ops
 from . import distributed as rfdist
 from .camera import CameraBounds, CameraIntrinsics, compute_thre3d_grid_sizes, mse2psnr, scale_camera_intrinsics
 from .constants import CAMERA_BOUNDS, CAMERA_INTRINSICS, HEMISPHERICAL_RADIUS
@@ -669,7 +669,7 @@ class TrainStepper:
                 flags |= _lib.FLAG_JITTER_KEYED
                 st.pass_[i].jitter_key, st.pass_[i].t_rand_dev = jit[i].key, None
             else:
-                st.pass_[i].t_rand_dev = None if jit[i] is None else jit[i].data_ptr()
+                st.pass_[i].t_rand_dev = _marshal.ptr(jit[i])
         st.flags = flags
         rf_grid = grid.to_rf_grid(use_occupancy=cfg.use_occupancy_mask, wait_parameters=self.exchange != "owner")
         opt = self.optimizer
@@ -684,15 +684,15 @@ class TrainStepper:
             ad = ex["adam"]
             ad.lr, ad.step = float(opt.lr), int(opt.step_count)
             first, second = grid.kernel_tensors()
-            ad.param_first_dev, ad.param_second_dev = first.data_ptr(), None if second is None else second.data_ptr()
+            ad.param_first_dev, ad.param_second_dev = first.data_ptr(), _marshal.ptr(second)
             st.adam = C.pointer(ad)
         else:
             st.adam = None
             gd, gf = self.flat.views_for_accumulation()
-            st.grad_first_dev, st.grad_second_dev = gd.data_ptr(), None if gf is None else gf.data_ptr()
+            st.grad_first_dev, st.grad_second_dev = gd.data_ptr(), _marshal.ptr(gf)
         st.timing_events = self.step_events.array if self.step_events is not None else None
         with ops._span("train_step", dev):
-            rc = _lib.load().rf_train_step(C.byref(rf_grid), C.byref(st), torch.cuda.current_stream(dev).cuda_stream)
+            rc = _lib.load().rf_train_step(C.byref(rf_grid), C.byref(st), _marshal.stream(dev))
         _lib.check(rc, "rf_train_step")
         tv = dist = None
         if self.fuse_optimizer:

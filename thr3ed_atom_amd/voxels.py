@@ -18,7 +18,7 @@ import torch
 from torch import Tensor
 from torch.nn import Module
 
-from . import _lib
+from . import _lib, _marshal
 from .camera import slack_range_map
 from .constants import COMPRESSED_STATE, CONFIG_DICT, STATE_DICT, THRE3D_REPR, u_DENSITIES, u_FEATURES
 
@@ -201,14 +201,14 @@ class KernelGridInterface:
         if mode is None or not (_is_identity(getattr(self, "_feature_preactivation", None)) and _is_identity(getattr(self, "_feature_postactivation", None))):
             raise ValueError("the fused HIP kernels implement Identity/ReLU, Identity/Softplus, torch.abs/Identity and Identity/Identity density activations "
                              "with identity feature activations; this grid's callables need the composed path (thr3ed_atom_amd.composable)")
-        key = (d.data_ptr(), None if f is None else f.data_ptr(), occ_ptr, self._aabb, self._expected_density_scale, mode, tuple(d.shape))
+        key = (d.data_ptr(), _marshal.ptr(f), occ_ptr, self._aabb, self._expected_density_scale, mode, tuple(d.shape))
         # (kept OUTSIDE the object: a ctypes struct with pointers in a module's __dict__ breaks copy.deepcopy / torch.save of it)
         cached = _RF_GRID_CACHE.get(self)
         if cached is not None and cached[0] == key:
             return cached[1]
         g = _lib.RFGrid()
         g.densities_dev = d.data_ptr()
-        g.features_dev = None if f is None else f.data_ptr()
+        g.features_dev = _marshal.ptr(f)
         for a in range(3):
             g.dims[a] = self.grid_dims[a]
             lo, hi = self._aabb[a]
@@ -262,13 +262,13 @@ class KernelGridInterface:
         g = _lib.RFGrid()
         C.memmove(C.byref(g), C.byref(real), C.sizeof(_lib.RFGrid))
         g.densities_dev = sh["base"].data_ptr()
-        g.features_dev = None if sh["rest"] is None else sh["rest"].data_ptr()
+        g.features_dev = _marshal.ptr(sh["rest"])
         g.density_stride, g.feature_stride = 4, 0 if sh["rest"] is None else int(sh["rest"].shape[-1])
         g.layout = _lib.LAYOUTS["split"]
         if refresh:
             stamp = self._shadow_stamp()
             if sh["stamp"] != stamp:
-                _lib.check(_lib.load().rf_convert_grid(C.byref(real), C.byref(g), torch.cuda.current_stream(d.device).cuda_stream), "rf_convert_grid")
+                _lib.check(_lib.load().rf_convert_grid(C.byref(real), C.byref(g), _marshal.stream(d.device)), "rf_convert_grid")
                 sh["stamp"] = stamp
         return sh, g
 
@@ -280,7 +280,7 @@ class KernelGridInterface:
         sh, g = self._shadow(refresh=False)
         if relayout:
             real = self.to_rf_grid()
-            _lib.check(_lib.load().rf_convert_grid(C.byref(g), C.byref(real), torch.cuda.current_stream(d.device).cuda_stream), "rf_convert_grid")
+            _lib.check(_lib.load().rf_convert_grid(C.byref(g), C.byref(real), _marshal.stream(d.device)), "rf_convert_grid")
         self.invalidate_occupancy()  # the densities changed
         sh["stamp"] = self._shadow_stamp()
 
@@ -292,7 +292,7 @@ class KernelGridInterface:
         dev = self.kernel_tensors()[0].device
         occ = torch.empty((ncell + 31) // 32, dtype=torch.int32, device=dev)
         grid = self.to_rf_grid()
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _marshal.stream(dev)
         _lib.check(_lib.load().rf_build_occupancy(grid, float(threshold), occ.data_ptr(), stream), "rf_build_occupancy")
         self._occupancy = occ
         d = self.kernel_tensors()[0]
@@ -702,7 +702,7 @@ def scale_voxel_grid_with_required_output_size(
             **voxel_grid.get_config_dict(),
             storage=voxel_grid.storage,
         )
-        stream = torch.cuda.current_stream(first.device).cuda_stream
+        stream = _marshal.stream(first.device)
         with torch.no_grad():
             _lib.check(_lib.load().rf_upsample_grid(voxel_grid.to_rf_grid(), new_grid.to_rf_grid(), stream), "rf_upsample_grid")
         return new_grid
