@@ -723,7 +723,8 @@ int rf_texture_bake(const RFGrid* grid, const float* vertices_dev, int64_t num_v
  *   neither; image row 0 on top, v = 1 there) the bilinear fetch at texel coordinates (u W_t - 1/2, (1 - v) H_t - 1/2) of the
  *   interpolated (u, v) = sum_k w_k uv_k, taps clamped to the image; else sum_k w_k colours_dev[v_k] (colours_dev [V, 3]).  The texture
  *   wins when both are given.  Pixels without a hit get 0, or 1 under RF_FLAG_WHITE_BKGD.  Both calls take the same camera, mesh and
- *   flag word.
+ *   flag word.  (rf_mesh_raster_taps, further down, records the four taps and two fractions of this fetch per pixel instead of
+ *   fetching through them: the same device code up to the fetch.)
  * Before any launch, in this order: RF_ERR_NULL_POINTER (camera, visibility_dev, status_dev / depth_dev, face_ids_dev, vertices_dev /
  * faces_dev with a non-zero count, uvs_dev and texture_dev given by halves, colour_dev without a texture or colours_dev);
  * RF_ERR_BAD_SHAPE (negative counts, num_faces >= 2^31, an image edge outside [1, 16384], a focal that is not finite or <= 0, a pose
@@ -769,6 +770,54 @@ int rf_texture_project_views(const float* vertices_dev, int64_t num_vertices, co
                              int32_t rows, int32_t num_views, const RFCamera* cameras, const float* images_dev, const uint64_t* visibility_dev,
                              const float* alphas_dev, float near, float depth_bias, float min_cos, int32_t cos_power, float background, uint32_t flags,
                              float* accum_dev, int32_t* count_dev, int32_t* status_dev, void* stream);
+
+/* ---- texture gradients of the mesh render (csrc/mesh_raster_kernels.hip and csrc/texture_fit_kernels.hip; DESIGN.md section 24;
+ * thr3ed_atom_amd/texture_fit.py builds the transposed tap list and runs the optimiser) ----------------------------------------------
+ * With mesh, UVs and cameras fixed the colour image of rf_mesh_raster_shade is a sparse linear map of the texture: four bilinear taps
+ * per hit pixel.  RFTextureTap is one pixel's row of it: the tap columns x0, x1 and rows y0, y1 (already clamped to the texture) and
+ * the fractions fx, fy; x0 == 0xFFFF marks a pixel without a hit (texture edges are at most 16384).
+ * rf_mesh_raster_taps: one lane per pixel over the visibility buffer rf_mesh_raster_visibility filled, with the camera, mesh and flag
+ *   word of that call.  taps_dev [H, W] holds exactly what rf_mesh_raster_shade computes before its fetch (both kernels call the same
+ *   two device functions), for the pixels it would give a face id >= 0; the others get x0 = x1 = y0 = y1 = 0xFFFF, fx = fy = 0.
+ *   Before any launch: RF_ERR_NULL_POINTER (camera, visibility_dev, taps_dev, vertices_dev / faces_dev / uvs_dev with a non-zero
+ *   count), RF_ERR_BAD_SHAPE (as rf_mesh_raster_shade; a texture edge outside [1, 16384]), RF_ERR_UNSUPPORTED (a flag bit other than
+ *   RF_FLAG_WHITE_BKGD and RF_RASTER_CULL_BACKFACES).
+ * rf_texture_sample: colour_dev [P, 3] from taps_dev [P] (the records of any number of views, P < 2^31) and texture_dev [H_t, W_t, 3]:
+ *   top = (1 - fx) T[y0, x0] + fx T[y0, x1], bot = (1 - fx) T[y1, x0] + fx T[y1, x1], colour = (1 - fy) top + fy bot -- the operations
+ *   of rf_mesh_raster_shade in its order, so the colours are its colours bit for bit -- and `background` where x0 == 0xFFFF.  A tap
+ *   outside the texture sets status_dev[0] (int32, zeroed by the caller) to 1 and gives the background; it is never dereferenced.
+ *   One lane per pixel, a pure gather.
+ * rf_texture_sample_backward: grad_texture_dev [H_t W_t, 3] = the transposed map applied to grad_colour_dev [P, 3], in gather form:
+ *   offsets_dev [H_t W_t + 1] int64 (ascending, offsets[0] = 0, offsets[H_t W_t] = num_entries) delimits every texel's segment of
+ *   entries_dev [num_entries] RFTextureTapEntry (pixel, weight), sorted by texel, ties in ascending pixel order.  Texel k gets
+ *   sum_e weight_e grad_colour[pixel_e] over its segment in float32 -- 0 for an empty one: EVERY texel is written, the caller clears
+ *   nothing.  A segment of at most `long_segment` entries (0: the library's default, 16) is summed by its own lane in entry order; a
+ *   longer one by the whole wavefront: lane l sums entries l, l + 64, ... in entry order, then the 64 partial sums are combined by
+ *   the fixed tree x_l += x_(l + 32), (l + 16), ..., (l + 1).  No atomics; the order of the additions depends on the entry list and
+ *   long_segment alone, so two calls give identical bits.  An entry whose pixel lies outside [0, P) sets status_dev[0] to 1 and is
+ *   skipped; it is never dereferenced.
+ * Before any launch, in this order: RF_ERR_NULL_POINTER (texture_dev / colour_dev / taps_dev, offsets_dev / grad_texture_dev /
+ * status_dev, grad_colour_dev / entries_dev with a non-zero count), RF_ERR_BAD_SHAPE (P < 0 or >= 2^31, a texture edge outside
+ * [1, 16384], a background that is not finite or negative, num_entries < 0 or >= 2^33, long_segment < 0), RF_ERR_UNSUPPORTED (any flag
+ * bit: none is defined).  P == 0 returns RF_OK from rf_texture_sample without a launch.  (Added to ABI version 4 compatibly: no
+ * existing struct or signature changed.) */
+typedef struct RFTextureTap {
+  uint16_t x0, x1, y0, y1;
+  float fx, fy;
+} RFTextureTap; /* 16 bytes */
+typedef struct RFTextureTapEntry {
+  int32_t pixel;
+  float weight;
+} RFTextureTapEntry; /* 8 bytes */
+/* (taps_dev and entries_dev are device arrays of the two records above, passed untyped like every device array of records) */
+int rf_mesh_raster_taps(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                        const uint64_t* visibility_dev, const float* uvs_dev, int32_t texture_height, int32_t texture_width, uint32_t flags,
+                        void* taps_dev, void* stream);
+int rf_texture_sample(const void* taps_dev, int64_t num_pixels, const float* texture_dev, int32_t texture_height, int32_t texture_width,
+                      float background, uint32_t flags, float* colour_dev, int32_t* status_dev, void* stream);
+int rf_texture_sample_backward(const float* grad_colour_dev, int64_t num_pixels, const int64_t* offsets_dev, const void* entries_dev,
+                               int64_t num_entries, int32_t texture_height, int32_t texture_width, int32_t long_segment, uint32_t flags,
+                               float* grad_texture_dev, int32_t* status_dev, void* stream);
 
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);

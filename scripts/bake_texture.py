@@ -21,6 +21,12 @@ depth test; texels that no view sees keep the normal-ray bake described above.  
 their poses instead (rf.bake_texture_from_views; the data options are those of scripts/train_sh_based_voxel_grid.py, the same views
 are held out).  --depth_bias (default: the mean edge length of the mesh), --min_cos and --cos_power are passed on.  Without --views and
 --dataset_views the script does what it did before.
+
+    python scripts/bake_texture.py -i model.pth --mesh small.ply -o textured --views 42 --fit_iterations 200
+
+--fit_iterations N (with --views or --dataset_views) then fits the baked texture to those same views by N Adam steps through the mesh
+render's texture gradient (rf.fit_texture / rf.fit_texture_to_field_views): --fit_lr, --fit_loss l2 | l1 and
+--fit_dssim_weight are passed on.  Without it nothing of the fit is allocated or launched.
 """
 import os
 import sys
@@ -60,7 +66,19 @@ def bake_from_views(config, model, extra, mesh, fallback, dev):
     seen = float((out.views > 0).sum()) / max(int((fallback.texture.sum(-1) != 0).sum()), 1)
     print(f"view bake from {source}: {int((out.views > 0).sum())} texels seen (about {100 * seen:.1f} % of the non-black texels of the normal-ray bake), "
           f"{1e3 * (time.perf_counter() - t0):.1f} ms (incl. the renders and host synchronisation)")
-    return out.bake
+    bake = out.bake
+    if config["fit_iterations"]:
+        fit = dict(iterations=config["fit_iterations"], lr=config["fit_lr"], loss=config["fit_loss"], dssim_weight=config["fit_dssim_weight"])
+        t0 = time.perf_counter()
+        if config["dataset_views"]:
+            fitted = rf.fit_texture(mesh, bake, images, poses, train.camera_intrinsics, **fit)
+        else:
+            fitted = rf.fit_texture_to_field_views(mesh, bake, model, poses, intr, **fit)
+        history = fitted.history.cpu()
+        print(f"texture fit ({config['fit_loss']}, D-SSIM weight {config['fit_dssim_weight']:.6g}, lr {config['fit_lr']:.6g}): loss {float(history[0]):.6g} -> {float(history[-1]):.6g} "
+              f"in {len(history)} iterations over {int((fitted.coverage > 0).sum())} texels, {1e3 * (time.perf_counter() - t0):.1f} ms (incl. the renders)")
+        bake = fitted.bake
+    return bake
 
 
 # fmt: off
@@ -83,6 +101,11 @@ def bake_from_views(config, model, extra, mesh, fallback, dev):
 @click.option("--depth_bias", type=click.FloatRange(min=0.0), default=None, required=False, help="how far behind the rasterised depth a texel may lie and still count as seen (default: the mean edge length)")
 @click.option("--min_cos", type=click.FloatRange(min=0.0, max=1.0, max_open=True), default=0.1, required=False, help="views at a flatter angle to the face than this cosine do not count")
 @click.option("--cos_power", type=click.IntRange(min=0, max=8), default=2, required=False, help="a view is weighted by the cosine to this power")
+# Fitting the baked texture to the views it was baked from (off unless --fit_iterations is given):
+@click.option("--fit_iterations", type=click.IntRange(min=0), default=0, required=False, help="Adam steps on the texture against the views of --views / --dataset_views")
+@click.option("--fit_lr", type=click.FloatRange(min=0.0, min_open=True), default=rf.texture_fit.DEFAULT_LR, required=False, help="learning rate of the fit")
+@click.option("--fit_loss", type=click.Choice(["l2", "l1"]), default="l2", required=False, help="the per-pixel loss of the fit")
+@click.option("--fit_dssim_weight", type=click.FloatRange(min=0.0, max=1.0), default=0.0, required=False, help="weight of 1 - SSIM in the loss of the fit")
 @click.option("-d", "--data_path", type=click.Path(), required=False, default=None, help=".npz with images, poses, focal, near, far (as for training)")
 @click.option("--data_downsample_factor", type=click.FloatRange(min=1.0), required=False, default=1.0, help="downscale factor for the input images")
 @click.option("--synthetic", type=click.BOOL, required=False, default=False, help="the procedural scene of the training script")
@@ -93,6 +116,8 @@ def main(**kwargs) -> None:
     config = dict(kwargs)
     if config["views"] is not None and config["dataset_views"]:
         raise click.UsageError("--views and --dataset_views exclude each other")
+    if config["fit_iterations"] and config["views"] is None and not config["dataset_views"]:
+        raise click.UsageError("--fit_iterations needs --views or --dataset_views")
     dev = torch.device("cuda:0")
     creator = lambda info: rf.create_voxel_grid_from_saved_info_dict(info, storage="split")  # noqa: E731
     model, extra = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)

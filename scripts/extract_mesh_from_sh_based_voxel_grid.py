@@ -19,7 +19,9 @@ leg, --texture_samples samples per texel and a ray of --texture_reach_voxels (sm
 (default: the simplification cell plus one voxel; two voxels without simplification).  Unset, nothing changes.
 --texture_views N (with --texture_patch) then re-bakes the texels a camera sees from the field's own renders over the turn-table of
 scripts/render_mesh.py with --num_frames N and the checkpoint's camera (rf.bake_texture_from_field_views); the
-texels no view sees keep the normal-ray bake.  scripts/bake_texture.py has the remaining options.
+texels no view sees keep the normal-ray bake.  --texture_fit_iterations N (with --texture_views) then fits the texture to those same
+renders by N Adam steps on the L2 error of the mesh render (rf.fit_texture_to_field_views); unset, nothing of the
+fit is allocated or launched.  scripts/bake_texture.py has the remaining options.
 
 --keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
 whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
@@ -58,6 +60,7 @@ import thr3ed_atom_amd as rf  # noqa: E402
 @click.option("--texture_reach_voxels", type=click.FloatRange(min=0.0), default=None, required=False, help="half length of a texel's ray, in (smallest) voxel edges")
 @click.option("--texture_samples", type=click.IntRange(min=1, max=256), default=16, required=False, help="samples per texel")
 @click.option("--texture_views", type=click.IntRange(min=2), default=None, required=False, help="with --texture_patch: re-bake the seen texels from the field's renders over a turn-table of this many frames")
+@click.option("--texture_fit_iterations", type=click.IntRange(min=0), default=0, required=False, help="with --texture_views: then fit the texture to those renders by this many Adam steps")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -70,6 +73,8 @@ def main(**kwargs) -> None:
     creator = lambda info: rf.create_voxel_grid_from_saved_info_dict(info, storage="split")  # noqa: E731
     if config["texture_views"] is not None and config["texture_patch"] is None:
         raise click.UsageError("--texture_views needs --texture_patch")
+    if config["texture_fit_iterations"] and config["texture_views"] is None:
+        raise click.UsageError("--texture_fit_iterations needs --texture_views")
     model, extra = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)
     grid = model.thre3d_repr
     iso = config["iso_level"]
@@ -118,6 +123,11 @@ def main(**kwargs) -> None:
             views = rf.bake_texture_from_field_views(mesh, model, poses, intr, config["texture_patch"], fallback=bake)
             print(f"texture: {int((views.views > 0).sum())} texels re-baked from {len(poses)} renders of {intr[0]}x{intr[1]}")
             bake = views.bake
+            if config["texture_fit_iterations"]:
+                fitted = rf.fit_texture_to_field_views(mesh, bake, model, poses, intr, iterations=config["texture_fit_iterations"])
+                history = fitted.history.cpu()
+                print(f"texture: fitted to the same renders, L2 loss {float(history[0]):.6g} -> {float(history[-1]):.6g} in {len(history)} iterations")
+                bake = fitted.bake
         torch.cuda.synchronize()
         stem = os.path.splitext(config["output_path"])[0]
         rf.write_obj(mesh, bake, stem)

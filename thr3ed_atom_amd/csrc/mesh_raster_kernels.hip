@@ -34,6 +34,10 @@
 // functions (the same bits), write depth, face_ids, optionally the barycentrics, and the colour: a bilinear fetch of the bake's
 // texture at the interpolated per-corner UVs (texel coordinates (u W_t - 1/2, (1 - v) H_t - 1/2), taps clamped to the image), or
 // sum_k w_k colour_k of the vertex colours.  Pixels without a hit get the background, depth 0 and face id -1.
+//
+// The taps pass (rf_mesh_raster_taps).  One lane per pixel, the shade pass up to its fetch: winning_hit and
+// texel_taps are the two device functions both kernels call, so a tap record holds the bits the shade kernel fetches through.
+// thr3ed_atom_amd/texture_fit.py turns the records of many views into the sparse matrix whose adjoint csrc/texture_fit_kernels.hip sums.
 #include "rf_device.h"
 
 namespace {
@@ -253,46 +257,56 @@ struct ShadeArgs {
   float* bary;  // or nullptr
 };
 
+// the winning face of a pixel as the visibility buffer recorded it (defined below the shade kernel)
+__device__ __forceinline__ bool winning_hit(const RasterArgs& a, unsigned long long key, int i, int j, long long& t, unsigned long long (&vi)[3], RasterHit& h);
+
+// the four taps of the bilinear fetch at the interpolated UVs of a hit: the ONLY place they are computed (the shade kernel fetches
+// through them, the taps kernel records them)
+struct TexelTaps {
+  int x0, x1, y0, y1;
+  float fx, fy;
+};
+
+__device__ __forceinline__ TexelTaps texel_taps(const float* uv, const float (&w)[3], int Ht, int Wt) {
+  const float u = (w[0] * uv[0] + w[1] * uv[2]) + w[2] * uv[4];
+  const float vv = (w[0] * uv[1] + w[1] * uv[3]) + w[2] * uv[5];
+  const float x = u * (float)Wt - 0.5f, y = (1.0f - vv) * (float)Ht - 0.5f;
+  const float xf = floorf(x), yf = floorf(y);
+  TexelTaps p;
+  p.fx = x - xf, p.fy = y - yf;
+  // (clamped as floats first, so that the conversion is defined for every value; NaN goes to 0)
+  p.x0 = (int)fminf(fmaxf(xf, 0.0f), (float)(Wt - 1)), p.x1 = (int)fminf(fmaxf(xf + 1.0f, 0.0f), (float)(Wt - 1));
+  p.y0 = (int)fminf(fmaxf(yf, 0.0f), (float)(Ht - 1)), p.y1 = (int)fminf(fmaxf(yf + 1.0f, 0.0f), (float)(Ht - 1));
+  return p;
+}
+
 __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterArgs a, ShadeArgs s) {
   const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
   if (pix >= (long long)a.cam.H * a.cam.W) return;
   const int i = (int)(pix / a.cam.W), j = (int)(pix - (long long)i * a.cam.W);
-  const unsigned long long key = s.vis[pix];
   float rgb[3] = {s.background, s.background, s.background}, w[3] = {0.0f, 0.0f, 0.0f}, z = 0.0f;
   int id = -1;
-  const long long t = (long long)(key & 0xffffffffull);
-  if (key != kNoHit && t < a.num_faces) {
-    unsigned long long vi[3];
-    float v[3][3];
-    if (load_face(a, t, vi, v, nullptr)) {
-      const RasterFace f = raster_face(a.cam, vi, v);
-      const RasterHit h = raster_hit(a.cam, f, i, j, a.cull);  // the bits the visibility pass saw
-      id = (int)t, z = h.z;
+  long long t;
+  unsigned long long vi[3];
+  RasterHit h;
+  if (winning_hit(a, s.vis[pix], i, j, t, vi, h)) {
+    id = (int)t, z = h.z;
 #pragma unroll
-      for (int k = 0; k < 3; ++k) w[k] = h.w[k];
-      if (s.colour && s.texture) {
-        const float* uv = s.uvs + 6 * t;
-        const float u = (w[0] * uv[0] + w[1] * uv[2]) + w[2] * uv[4];
-        const float vv = (w[0] * uv[1] + w[1] * uv[3]) + w[2] * uv[5];
-        const float x = u * (float)s.Wt - 0.5f, y = (1.0f - vv) * (float)s.Ht - 0.5f;
-        const float xf = floorf(x), yf = floorf(y);
-        const float fx = x - xf, fy = y - yf;
-        // (clamped as floats first, so that the conversion is defined for every value; NaN goes to 0)
-        const int x0 = (int)fminf(fmaxf(xf, 0.0f), (float)(s.Wt - 1)), x1 = (int)fminf(fmaxf(xf + 1.0f, 0.0f), (float)(s.Wt - 1));
-        const int y0 = (int)fminf(fmaxf(yf, 0.0f), (float)(s.Ht - 1)), y1 = (int)fminf(fmaxf(yf + 1.0f, 0.0f), (float)(s.Ht - 1));
-        const float* r0 = s.texture + 3ll * ((long long)y0 * s.Wt);
-        const float* r1 = s.texture + 3ll * ((long long)y1 * s.Wt);
+    for (int k = 0; k < 3; ++k) w[k] = h.w[k];
+    if (s.colour && s.texture) {
+      const TexelTaps p = texel_taps(s.uvs + 6 * t, w, s.Ht, s.Wt);
+      const float* r0 = s.texture + 3ll * ((long long)p.y0 * s.Wt);
+      const float* r1 = s.texture + 3ll * ((long long)p.y1 * s.Wt);
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-          const float top = (1.0f - fx) * r0[3 * x0 + ch] + fx * r0[3 * x1 + ch];
-          const float bot = (1.0f - fx) * r1[3 * x0 + ch] + fx * r1[3 * x1 + ch];
-          rgb[ch] = (1.0f - fy) * top + fy * bot;
-        }
-      } else if (s.colour && s.colours) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch)
-          rgb[ch] = (w[0] * s.colours[3 * vi[0] + ch] + w[1] * s.colours[3 * vi[1] + ch]) + w[2] * s.colours[3 * vi[2] + ch];
+      for (int ch = 0; ch < 3; ++ch) {
+        const float top = (1.0f - p.fx) * r0[3 * p.x0 + ch] + p.fx * r0[3 * p.x1 + ch];
+        const float bot = (1.0f - p.fx) * r1[3 * p.x0 + ch] + p.fx * r1[3 * p.x1 + ch];
+        rgb[ch] = (1.0f - p.fy) * top + p.fy * bot;
       }
+    } else if (s.colour && s.colours) {
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)
+        rgb[ch] = (w[0] * s.colours[3 * vi[0] + ch] + w[1] * s.colours[3 * vi[1] + ch]) + w[2] * s.colours[3 * vi[2] + ch];
     }
   }
   s.depth[pix] = z;
@@ -305,6 +319,36 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterA
 #pragma unroll
     for (int k = 0; k < 3; ++k) s.bary[3 * pix + k] = w[k];
   }
+}
+
+// the winning face of a pixel as the visibility buffer recorded it: false when nothing was hit (or the key names no face of this
+// mesh); else t, vi and the hit re-evaluated with the device functions of the visibility pass (the same bits)
+__device__ __forceinline__ bool winning_hit(const RasterArgs& a, unsigned long long key, int i, int j, long long& t, unsigned long long (&vi)[3], RasterHit& h) {
+  t = (long long)(key & 0xffffffffull);
+  if (key == kNoHit || t >= a.num_faces) return false;
+  float v[3][3];
+  if (!load_face(a, t, vi, v, nullptr)) return false;
+  h = raster_hit(a.cam, raster_face(a.cam, vi, v), i, j, a.cull);
+  return true;
+}
+
+// one record per pixel: what the shade kernel computes before its fetch (x0 = 0xffff: no hit; texture edges are at most 16384)
+__global__ __launch_bounds__(kRasterBlock) void mesh_raster_taps_kernel(RasterArgs a, const unsigned long long* vis, const float* uvs, int Ht, int Wt, RFTextureTap* taps) {
+  const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
+  if (pix >= (long long)a.cam.H * a.cam.W) return;
+  const int i = (int)(pix / a.cam.W), j = (int)(pix - (long long)i * a.cam.W);
+  RFTextureTap rec;
+  rec.x0 = rec.x1 = rec.y0 = rec.y1 = 0xffffu;
+  rec.fx = rec.fy = 0.0f;
+  long long t;
+  unsigned long long vi[3];
+  RasterHit h;
+  if (winning_hit(a, vis[pix], i, j, t, vi, h)) {
+    const TexelTaps p = texel_taps(uvs + 6 * t, h.w, Ht, Wt);
+    rec.x0 = (uint16_t)p.x0, rec.x1 = (uint16_t)p.x1, rec.y0 = (uint16_t)p.y0, rec.y1 = (uint16_t)p.y1;
+    rec.fx = p.fx, rec.fy = p.fy;
+  }
+  taps[pix] = rec;
 }
 
 // the checks both entry points share, after their pointer checks: RF_ERR_BAD_SHAPE, then RF_ERR_UNSUPPORTED
@@ -370,6 +414,22 @@ int rf_mesh_raster_shade(const RFCamera* camera, const float* vertices_dev, int6
   s.colour = colour_dev, s.depth = depth_dev, s.face_ids = face_ids_dev, s.bary = barycentrics_dev;
   const long long total = (long long)camera->height * camera->width;  // <= 2^28
   hipLaunchKernelGGL(mesh_raster_shade_kernel, dim3((unsigned)((total + kRasterBlock - 1) / kRasterBlock)), dim3(kRasterBlock), 0, (hipStream_t)stream, a, s);
+  return launch_status();
+}
+
+int rf_mesh_raster_taps(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                        const uint64_t* visibility_dev, const float* uvs_dev, int32_t texture_height, int32_t texture_width, uint32_t flags,
+                        void* taps_dev, void* stream) {
+  if (!camera || !visibility_dev || !taps_dev) return RF_ERR_NULL_POINTER;
+  if ((num_vertices > 0 && !vertices_dev) || (num_faces > 0 && (!faces_dev || !uvs_dev))) return RF_ERR_NULL_POINTER;
+  const int rc = check_raster(camera, num_vertices, num_faces, 0.0f, 0u);
+  if (rc != RF_OK) return rc;
+  if (texture_height < 1 || texture_height > kMaxImageEdge || texture_width < 1 || texture_width > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
+  if (flags & ~(uint32_t)(RF_FLAG_WHITE_BKGD | RF_RASTER_CULL_BACKFACES)) return RF_ERR_UNSUPPORTED;
+  const RasterArgs a = raster_args(camera, vertices_dev, num_vertices, faces_dev, num_faces, 0.0f, flags);
+  const long long total = (long long)camera->height * camera->width;  // <= 2^28
+  hipLaunchKernelGGL(mesh_raster_taps_kernel, dim3((unsigned)((total + kRasterBlock - 1) / kRasterBlock)), dim3(kRasterBlock), 0, (hipStream_t)stream, a,
+                     (const unsigned long long*)visibility_dev, uvs_dev, texture_height, texture_width, (RFTextureTap*)taps_dev);
   return launch_status();
 }
 
