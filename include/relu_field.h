@@ -819,6 +819,56 @@ int rf_texture_sample_backward(const float* grad_colour_dev, int64_t num_pixels,
                                int64_t num_entries, int32_t texture_height, int32_t texture_width, int32_t long_segment, uint32_t flags,
                                float* grad_texture_dev, int32_t* status_dev, void* stream);
 
+/* ---- geometry gradients of the mesh render (csrc/mesh_fit_kernels.hip, which includes csrc/mesh_raster_kernels.hip for its
+ * device functions with RF_MESH_RASTER_DEVICE_ONLY defined; DESIGN.md section 25;
+ * thr3ed_atom_amd/mesh_fit.py sorts the hit pixels, builds the corner lists and runs the optimiser) -------------------------------
+ * Two images per view that are differentiable with respect to vertices_dev, in the rasteriser's own quantities (d, p_k = v_k - o,
+ * e_k, s, w_k = e_k / s, z as defined above, computed by the device functions the visibility and shade kernels call):
+ *   DEPTH     D[i, j] = z of the winning face at hit pixels, 0 elsewhere: the bits of rf_mesh_raster_shade.  At a hit pixel with
+ *             winning face (v0, v1, v2): dz/dv_k = w_k n / s with n = (v1 - v0) x (v2 - v0).  (Moving corner k by delta moves the
+ *             face's plane; its hit moves along the ray by w_k (n . delta) / (n . d), n . d = s, and d has camera-z -1, so the ray
+ *             parameter is the camera depth.)
+ *   COVERAGE  A[i, j] in [0, 1]: the edge-crossing anti-aliasing of nvdiffrast restricted to pairs of a HIT pixel a (winning face F)
+ *             and a 4-neighbour b inside the image that is a MISS.  F's edge values at both centres, sigma = sign(s(a)); for every k
+ *             with sigma e_k(b) < 0: tau_k = e_k(a) / (e_k(a) - e_k(b)); tau = min_k tau_k (the lowest k on ties) clamped to
+ *             [0, 1] -- where F's silhouette crosses the segment, measured from a's centre.  No such k (F covers b's centre but was
+ *             rejected there, by `near` for example): the pair contributes nothing.  b gains max(tau - 1/2, 0), a loses
+ *             max(1/2 - tau, 0).  Miss pixel: A = min(1, sum over its hit neighbours of the gains); hit pixel: A = max(0, 1 - sum
+ *             over its miss neighbours of the losses); float32 sums in the order left, right, up, down; pixels outside the image
+ *             are no neighbours.  Hit and miss are the visibility buffer's, so `near` and culling act through it.
+ * rf_mesh_raster_coverage: one lane per pixel over the visibility buffer rf_mesh_raster_visibility filled, with that call's camera,
+ *   mesh and cull flag; writes depth_dev, coverage_dev [H, W] float32 and face_ids_dev [H, W] int32 (-1: miss).  No atomics.
+ * rf_mesh_geometry_backward_pixels: one lane per pixel of ONE view, given the face_ids_dev and coverage_dev the forward wrote and the
+ *   upstream grad_depth_dev, grad_coverage_dev [H, W].  A hit pixel writes records_dev[pixel] = 9 floats, the gradient on the three
+ *   corners of its winning face: grad_depth w_k n / s, plus for every pair (itself, a missed neighbour b) with minimising edge k
+ *   (corners k1 = k + 1, k2 = k + 2 mod 3): G p_k2 x D on corner k1 and G D x p_k1 on corner k2, D = (e_k(a) d_b - e_k(b) d_a) /
+ *   (e_k(a) - e_k(b))^2 (e_k = d . (p_k1 x p_k2) is linear in the ray), G = [tau > 1/2][A(b) < 1] grad_coverage(b) +
+ *   [tau < 1/2][A(a) > 0] grad_coverage(a).  Saturation (A(b) = 1, A(a) = 0) is decided from the SAVED coverage image and passes no
+ *   gradient; tau = 1/2 exactly passes none either.  Both terms of a pair are owned by the hit pixel.  Miss pixels write NOTHING
+ *   (their records are never read).  A face id >= num_faces or a vertex index outside [0, num_vertices) sets status_dev[0] to 1 and
+ *   the pixel's record is written as 0.  num_faces == 0 returns RF_OK without a launch.
+ * rf_mesh_geometry_backward_gather: grad_vertices_dev [V, 3] from the records of all views (records_dev [num_pixels, 9]) by two
+ *   segmented sums without atomics.  hit_pixels_dev [num_hits] int32: the hit pixels sorted by face id, ties in ascending pixel order;
+ *   face_offsets_dev [num_faces + 1] int64 delimits each face's segment; face_grads_dev [num_faces, 9] (scratch, every row written)
+ *   gets the per-face sums.  corner_slots_dev [3 num_faces] int32: the slots 3 face + corner sorted by the vertex they name, ascending
+ *   within a vertex; vertex_offsets_dev [V + 1] int64 delimits them; vertex v gets the sum of face_grads[slot] over its segment, 0
+ *   for an empty one (EVERY vertex is written).  A segment of at most `long_segment` entries (0: the default, 16) is summed by its
+ *   own lane in entry order, a longer one by the whole wavefront: lane l sums entries l, l + 64, ..., then the fixed tree
+ *   x_l += x_(l + 32), (l + 16), ..., (l + 1).  The additions and their order depend on the lists and long_segment alone: two calls
+ *   give identical bits.  An entry outside its rows sets status_dev[0] to 1 and is skipped; offsets are clamped to the list.
+ * Before any launch, in this order: RF_ERR_NULL_POINTER (any array a non-zero count needs, camera, status_dev); RF_ERR_BAD_SHAPE (as
+ * rf_mesh_raster_shade; num_pixels >= 2^31, num_hits > num_pixels, 3 num_faces >= 2^31, a negative count or long_segment);
+ * RF_ERR_UNSUPPORTED (a flag bit other than RF_RASTER_CULL_BACKFACES; any flag bit for the gather).  (Added to ABI version 4
+ * compatibly: no existing struct or signature changed.) */
+int rf_mesh_raster_coverage(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                            const uint64_t* visibility_dev, uint32_t flags, float* depth_dev, float* coverage_dev, int32_t* face_ids_dev, void* stream);
+int rf_mesh_geometry_backward_pixels(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                                     const int32_t* face_ids_dev, const float* coverage_dev, const float* grad_depth_dev, const float* grad_coverage_dev,
+                                     uint32_t flags, float* records_dev, int32_t* status_dev, void* stream);
+int rf_mesh_geometry_backward_gather(const float* records_dev, int64_t num_pixels, const int32_t* hit_pixels_dev, int64_t num_hits, const int64_t* face_offsets_dev,
+                                     int64_t num_faces, const int32_t* corner_slots_dev, const int64_t* vertex_offsets_dev, int64_t num_vertices,
+                                     int32_t long_segment, uint32_t flags, float* face_grads_dev, float* grad_vertices_dev, int32_t* status_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

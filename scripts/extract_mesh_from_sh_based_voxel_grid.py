@@ -23,6 +23,11 @@ texels no view sees keep the normal-ray bake.  --texture_fit_iterations N (with 
 renders by N Adam steps on the L2 error of the mesh render (rf.fit_texture_to_field_views); unset, nothing of the
 fit is allocated or launched.  scripts/bake_texture.py has the remaining options.
 
+--geometry_fit_iterations N moves the (simplified) mesh's vertices towards the field's own median depth and accumulated weight over a
+turn-table of --geometry_fit_views frames by N Adam steps (rf.fit_mesh_to_field_views), each vertex at most one
+clustering cell (two voxels without simplification) from where it started.  It runs after the simplification and before any texture
+bake, so the bake sees the fitted surface.  Off by default: unset, nothing of it is allocated or launched.
+
 --keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
 whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
 not touched.
@@ -61,6 +66,8 @@ import thr3ed_atom_amd as rf  # noqa: E402
 @click.option("--texture_samples", type=click.IntRange(min=1, max=256), default=16, required=False, help="samples per texel")
 @click.option("--texture_views", type=click.IntRange(min=2), default=None, required=False, help="with --texture_patch: re-bake the seen texels from the field's renders over a turn-table of this many frames")
 @click.option("--texture_fit_iterations", type=click.IntRange(min=0), default=0, required=False, help="with --texture_views: then fit the texture to those renders by this many Adam steps")
+@click.option("--geometry_fit_iterations", type=click.IntRange(min=0), default=0, required=False, help="fit the vertices to the field's depth and alpha renders by this many Adam steps")
+@click.option("--geometry_fit_views", type=click.IntRange(min=2), default=42, required=False, help="with --geometry_fit_iterations: frames of the turn-table the fit looks from")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -107,6 +114,17 @@ def main(**kwargs) -> None:
         cell_voxels = stats.cell_size / min(grid.voxel_size)
         summary = (f"simplified ({config['simplify_placement']}, cell size {stats.cell_size:.6g}): V = {extracted[0]} -> {len(mesh.vertices)}, "
                    f"T = {extracted[1]} -> {len(mesh.faces)} in {1e3 * (time.perf_counter() - t1):.1f} ms\n")
+    if config["geometry_fit_iterations"] and len(mesh.faces):
+        t3 = time.perf_counter()
+        intr = (extra or {}).get("camera_intrinsics", rf.CameraIntrinsics(800, 800, 1111.111))
+        poses = rf.get_thre360_animation_poses((extra or {}).get("hemispherical_radius", 4.0311), 60.0, config["geometry_fit_views"] + 1)  # (the path drops its last frame)
+        cell = (2.0 if cell_voxels is None else cell_voxels) * min(grid.voxel_size)
+        fitted = rf.fit_mesh_to_field_views(mesh, model, poses, intr, iterations=config["geometry_fit_iterations"], max_move=cell)
+        history = fitted.history.cpu()
+        mesh = fitted.mesh
+        torch.cuda.synchronize()
+        summary += (f"geometry: fitted to {len(poses)} views of the field, loss {float(history[0]):.6g} -> {float(history[-1]):.6g} in {len(history)} iterations, vertices moved "
+                    f"{float(fitted.moved.mean()):.4g} on average and at most {float(fitted.moved.max()):.4g} (limit {cell:.4g}) in {1e3 * (time.perf_counter() - t3):.1f} ms\n")
     out_dir = os.path.dirname(os.path.abspath(config["output_path"]))
     os.makedirs(out_dir, exist_ok=True)
     rf.write_ply(mesh, config["output_path"])

@@ -1,0 +1,74 @@
+#!/usr/bin/env python
+"""Fit the vertices of a triangle mesh (a binary PLY as ``write_ply``, scripts/extract_mesh_from_sh_based_voxel_grid.py and
+scripts/simplify_mesh.py write it) to the field it came from: Adam on the vertex positions against the field's own median depth and
+accumulated weight over a turn-table of views, through the anti-aliased coverage and the depth of the mesh rasteriser
+(rf.fit_mesh_to_field_views).  Faces and colours pass through; normals are recomputed when the PLY had them.
+
+    python scripts/fit_mesh.py -i model.pth --mesh small.ply -o fitted.ply --views 42 --iterations 200
+
+The views are those of scripts/render_mesh.py and scripts/bake_texture.py (--views N frames at --camera_pitch; the checkpoint's camera
+unless --view_height / --view_width / --view_focal say otherwise).  --max_move_voxels limits how far a vertex may go from where it
+started, in (smallest) voxel edges.  Bake textures AFTER the fit (scripts/bake_texture.py), so that they see the fitted surface.
+"""
+import os
+import sys
+import time
+
+import click
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import thr3ed_atom_amd as rf  # noqa: E402
+from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
+
+
+# fmt: off
+@click.command()
+@click.option("-i", "--model_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="path to the trained (reconstructed) model")
+@click.option("--mesh", "mesh_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="the .ply file to fit")
+@click.option("-o", "--output_path", type=click.Path(file_okay=True, dir_okay=False), required=True, help="the .ply file to write")
+@click.option("--views", type=click.IntRange(min=2), default=42, required=False, help="frames of the turn-table the fit looks from")
+@click.option("--iterations", type=click.IntRange(min=0), default=200, required=False, help="Adam steps")
+@click.option("--lr", type=click.FloatRange(min=0.0, min_open=True), default=None, required=False, help="step size in world units (default: 0.05 x the mean edge length)")
+@click.option("--depth_weight", type=click.FloatRange(min=0.0), default=1.0, required=False, help="weight of the depth term")
+@click.option("--mask_weight", type=click.FloatRange(min=0.0), default=1.0, required=False, help="weight of the coverage term")
+@click.option("--laplacian_weight", type=click.FloatRange(min=0.0), default=rf.mesh_fit.DEFAULT_LAPLACIAN_WEIGHT, required=False, help="weight of the Laplacian term (relative to the input mesh)")
+@click.option("--max_move_voxels", type=click.FloatRange(min=0.0, min_open=True), default=2.0, required=False, help="how far a vertex may move, in (smallest) voxel edges")
+@click.option("--camera_pitch", type=click.FLOAT, default=60.0, required=False, help="pitch of the turn-table, in degrees")
+@click.option("--view_height", type=click.IntRange(min=1), default=None, required=False, help="image height of the views (default: the checkpoint's camera)")
+@click.option("--view_width", type=click.IntRange(min=1), default=None, required=False, help="image width of the views (default: the checkpoint's camera)")
+@click.option("--view_focal", type=click.FLOAT, default=None, required=False, help="focal length of the views in pixels (default: the checkpoint's camera)")
+@click.option("--cull_backfaces", is_flag=True, default=False, help="draw only the faces whose outside looks at the camera")
+# fmt: on
+def main(**kwargs) -> None:
+    config = dict(kwargs)
+    dev = torch.device("cuda:0")
+    creator = lambda info: rf.create_voxel_grid_from_saved_info_dict(info, storage="split")  # noqa: E731
+    model, extra = rf.create_volumetric_model_from_saved_model(config["model_path"], creator, device=dev)
+    grid = model.thre3d_repr
+    vertices, normals, colours, faces = read_ply(config["mesh_path"])
+    on_device = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    mesh = rf.Mesh(on_device(vertices), on_device(faces), on_device(colours.astype(np.float32) / np.float32(255.0)), on_device(normals) if np.any(normals) else None)
+    intr = (extra or {}).get("camera_intrinsics", rf.CameraIntrinsics(800, 800, 1111.111))
+    intr = rf.CameraIntrinsics(config["view_height"] or intr[0], config["view_width"] or intr[1], config["view_focal"] or intr[2])
+    radius = (extra or {}).get("hemispherical_radius", 4.0311)
+    poses = rf.get_thre360_animation_poses(radius, config["camera_pitch"], config["views"] + 1)  # (the path drops its last frame)
+    limit = config["max_move_voxels"] * min(grid.voxel_size)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fit = rf.fit_mesh_to_field_views(mesh, model, poses, intr, iterations=config["iterations"], lr=config["lr"], depth_weight=config["depth_weight"],
+                                     mask_weight=config["mask_weight"], laplacian_weight=config["laplacian_weight"], max_move=limit, cull_backfaces=config["cull_backfaces"])
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    os.makedirs(os.path.dirname(os.path.abspath(config["output_path"])), exist_ok=True)
+    rf.write_ply(fit.mesh, config["output_path"])
+    history = fit.history.cpu()
+    ends = f"{float(history[0]):.6g} -> {float(history[-1]):.6g}" if len(history) else "(not run)"
+    print(f"mesh fit: loss {ends} in {len(history)} iterations over {len(poses)} views of {intr[0]}x{intr[1]} (radius {radius:.6g}, pitch {config['camera_pitch']:.6g}); "
+          f"V = {len(mesh.vertices)}, T = {len(mesh.faces)}; vertices moved {float(fit.moved.mean()) if len(mesh.vertices) else 0.0:.4g} on average, at most "
+          f"{float(fit.moved.max()) if len(mesh.vertices) else 0.0:.4g} (limit {limit:.4g}) in {dt:.2f} s (incl. the field's renders) -> {config['output_path']}")
+
+
+if __name__ == "__main__":
+    main()

@@ -38,6 +38,10 @@
 // The taps pass (rf_mesh_raster_taps).  One lane per pixel, the shade pass up to its fetch: winning_hit and
 // texel_taps are the two device functions both kernels call, so a tap record holds the bits the shade kernel fetches through.
 // thr3ed_atom_amd/texture_fit.py turns the records of many views into the sparse matrix whose adjoint csrc/texture_fit_kernels.hip sums.
+//
+// csrc/mesh_fit_kernels.hip needs the device functions of this file -- the face set-up, the edge values, the
+// coverage rule, winning_key, the argument checks -- with the bits they have here, so it includes this file with
+// RF_MESH_RASTER_DEVICE_ONLY defined: the kernels and the entry points below are then left out, everything else is the same text.
 #include "rf_device.h"
 
 namespace {
@@ -104,16 +108,22 @@ struct RasterHit {
   float w[3], z;
 };
 
-// the coverage rule, the barycentrics and the depth of pixel (i, j) on one face: the ONLY place they are computed
-__device__ __forceinline__ RasterHit raster_hit(const RasterCamera& cam, const RasterFace& f, int i, int j, int cull) {
-  float d[3], e[3];
+// the edge values e_k of pixel (i, j) on one face and their sum s = (e0 + e1) + e2: the ONLY place they are computed
+__device__ __forceinline__ float raster_edges(const RasterCamera& cam, const RasterFace& f, int i, int j, float (&e)[3]) {
+  float d[3];
   pixel_ray(i, j, cam.H, cam.W, cam.focal, cam.R, d);
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const float t = (f.c[k][0] * d[0] + f.c[k][1] * d[1]) + f.c[k][2] * d[2];
     e[k] = f.flip[k] ? -t : t;
   }
-  const float s = (e[0] + e[1]) + e[2];
+  return (e[0] + e[1]) + e[2];
+}
+
+// the coverage rule, the barycentrics and the depth of pixel (i, j) on one face: the ONLY place they are computed
+__device__ __forceinline__ RasterHit raster_hit(const RasterCamera& cam, const RasterFace& f, int i, int j, int cull) {
+  float e[3];
+  const float s = raster_edges(cam, f, i, j, e);
   const bool neg = e[0] <= 0.0f && e[1] <= 0.0f && e[2] <= 0.0f, pos = e[0] >= 0.0f && e[1] >= 0.0f && e[2] >= 0.0f;
   RasterHit h;
   h.hit = (neg || (pos && !cull)) && s != 0.0f;
@@ -140,6 +150,7 @@ __device__ __forceinline__ bool load_face(const RasterArgs& a, long long t, unsi
   return true;
 }
 
+#ifndef RF_MESH_RASTER_DEVICE_ONLY
 // The conservative pixel box [j0, j1] x [i0, i1] of a face whose corners all have z_k >= near >= 0: the projected corners, widened by
 // a bound on the float32 error of the projection plus one pixel, clipped to the image.  A corner whose depth is not safely positive
 // (or anything not finite) gives the whole image: conservative is all the box has to be, the coverage rule decides.
@@ -244,6 +255,8 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_visibility_kernel(Ra
   }
 }
 
+#endif  // RF_MESH_RASTER_DEVICE_ONLY
+
 struct ShadeArgs {
   const unsigned long long* vis;
   const float* uvs;      // [T, 3, 2] or nullptr
@@ -256,6 +269,13 @@ struct ShadeArgs {
   int* face_ids;
   float* bary;  // or nullptr
 };
+
+// the face index t a visibility key names: false when nothing was hit or the key names no face of this mesh (the shade pass then gives
+// the face id -1); csrc/mesh_fit_kernels.hip decodes its keys with this function too
+__device__ __forceinline__ bool winning_key(const RasterArgs& a, unsigned long long key, long long& t) {
+  t = (long long)(key & 0xffffffffull);
+  return !(key == kNoHit || t >= a.num_faces);
+}
 
 // the winning face of a pixel as the visibility buffer recorded it (defined below the shade kernel)
 __device__ __forceinline__ bool winning_hit(const RasterArgs& a, unsigned long long key, int i, int j, long long& t, unsigned long long (&vi)[3], RasterHit& h);
@@ -280,6 +300,7 @@ __device__ __forceinline__ TexelTaps texel_taps(const float* uv, const float (&w
   return p;
 }
 
+#ifndef RF_MESH_RASTER_DEVICE_ONLY
 __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterArgs a, ShadeArgs s) {
   const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
   if (pix >= (long long)a.cam.H * a.cam.W) return;
@@ -321,17 +342,19 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterA
   }
 }
 
+#endif  // RF_MESH_RASTER_DEVICE_ONLY
+
 // the winning face of a pixel as the visibility buffer recorded it: false when nothing was hit (or the key names no face of this
 // mesh); else t, vi and the hit re-evaluated with the device functions of the visibility pass (the same bits)
 __device__ __forceinline__ bool winning_hit(const RasterArgs& a, unsigned long long key, int i, int j, long long& t, unsigned long long (&vi)[3], RasterHit& h) {
-  t = (long long)(key & 0xffffffffull);
-  if (key == kNoHit || t >= a.num_faces) return false;
+  if (!winning_key(a, key, t)) return false;
   float v[3][3];
   if (!load_face(a, t, vi, v, nullptr)) return false;
   h = raster_hit(a.cam, raster_face(a.cam, vi, v), i, j, a.cull);
   return true;
 }
 
+#ifndef RF_MESH_RASTER_DEVICE_ONLY
 // one record per pixel: what the shade kernel computes before its fetch (x0 = 0xffff: no hit; texture edges are at most 16384)
 __global__ __launch_bounds__(kRasterBlock) void mesh_raster_taps_kernel(RasterArgs a, const unsigned long long* vis, const float* uvs, int Ht, int Wt, RFTextureTap* taps) {
   const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
@@ -350,6 +373,8 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_taps_kernel(RasterAr
   }
   taps[pix] = rec;
 }
+
+#endif  // RF_MESH_RASTER_DEVICE_ONLY
 
 // the checks both entry points share, after their pointer checks: RF_ERR_BAD_SHAPE, then RF_ERR_UNSUPPORTED
 int check_raster(const RFCamera* cam, int64_t num_vertices, int64_t num_faces, float near, uint32_t flags) {
@@ -378,6 +403,7 @@ RasterArgs raster_args(const RFCamera* cam, const float* vertices, int64_t num_v
 
 }  // namespace
 
+#ifndef RF_MESH_RASTER_DEVICE_ONLY
 extern "C" {
 
 int rf_mesh_raster_visibility(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
@@ -434,3 +460,4 @@ int rf_mesh_raster_taps(const RFCamera* camera, const float* vertices_dev, int64
 }
 
 }  // extern "C"
+#endif  // RF_MESH_RASTER_DEVICE_ONLY
