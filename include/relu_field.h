@@ -869,6 +869,42 @@ int rf_mesh_geometry_backward_gather(const float* records_dev, int64_t num_pixel
                                      int64_t num_faces, const int32_t* corner_slots_dev, const int64_t* vertex_offsets_dev, int64_t num_vertices,
                                      int32_t long_segment, uint32_t flags, float* face_grads_dev, float* grad_vertices_dev, int32_t* status_dev, void* stream);
 
+/* ---- TSDF fusion of posed depth views (csrc/fusion_kernels.hip; thr3ed_atom_amd/fusion.py chunks the views,
+ * finalises and hands the volume to rf_mesh_count / rf_mesh_emit as an identity-mode grid) ----------------------------------------
+ * The volume is a lattice of dims = (X, Y, Z) nodes in the box [aabb_min, aabb_max] (HOST arrays of 3), placed as an RFGrid's nodes
+ * are: node (ix, iy, iz) sits at aabb_min + (aabb_max - aabb_min) * ((2i + 1) / (2 dim)) per axis in float32 (the interior lattice
+ * points of rf_mesh_count at subdivisions = 1) and has plain index n = (ix Y + iy) Z + iz.  `cameras` is a HOST array of num_views
+ * (0 .. 16) RFCamera of one height H and width W (focals and poses are free); depths_dev [n, H, W] float32, the ray parameter of the
+ * first surface per pixel (= the camera-space depth: what rf_mesh_raster_shade and rf_render_geometry write); alphas_dev [n, H, W]
+ * float32 or NULL; images_dev [n, H, W, 3] float32 or NULL.  tsdf_sum_dev [N] float32, counts_dev [N, 2] int32 = (observed, hidden)
+ * and colour_sum_dev [N, 4] float32 (three colour sums and their count; required with images_dev, else NULL or carried through) are
+ * IN/OUT; counts_dev is 8-byte and colour_sum_dev 16-byte aligned.  Per node p, for each view k in order:
+ *   1. c = R_k^T (p - t_k), z = -c_z (the products and the sum order of rf_texture_project_views); skipped unless z is finite and
+ *      z > near.
+ *   2. x = W/2 + f c_x / z, y = H/2 - f c_y / z; skipped unless 0 <= x < W and 0 <= y < H; j = floor(x), i = floor(y).  The fetch is
+ *      nearest-pixel: interpolating depth across a discontinuity invents surfaces.
+ *   3. D = depths[k, i, j], A = alphas[k, i, j] when alphas are given.  D not finite: skipped (no information).  The pixel is a MISS
+ *      when D <= 0, or when alphas are given and A < min_alpha; otherwise a hit.
+ *   4. Miss: under RF_FUSE_CARVE the ray crosses the node in free space, s = 1, observed; without the flag: skipped.
+ *   5. Hit: sdf = D - z.  sdf < -truncation: HIDDEN, counts.hidden += 1 and nothing else.  Otherwise s = min(1, sdf / truncation),
+ *      observed.
+ *   6. Observed: tsdf_sum += s, counts.observed += 1.
+ *   7. With images, a hit with |sdf| <= truncation: colour_sum.rgb += images[k, i, j, :], colour_sum.w += 1.
+ * Weights are 1: no angle weights, no running-average cap, no bilinear fetch.  One launch, one lane per node, no atomics: the lane
+ * loads its accumulators, adds its views in order and stores them, so two calls give identical bits and successive calls over
+ * chunks of views do the float additions of one long loop; a node no view of the chunk touches gets back what was loaded.  Every
+ * pixel index is formed only after the tests of step 2 held (NaN fails them).  Before any launch, in this order:
+ * RF_ERR_NULL_POINTER (the box, dims, tsdf_sum_dev, counts_dev; cameras / depths_dev with num_views > 0; images_dev without
+ * colour_sum_dev), RF_ERR_BAD_SHAPE (a dim outside [1, 4096] or N >= 2^31, a box that is not finite or has max <= min on an axis,
+ * num_views outside [0, 16], an image edge outside [1, 16384], views of unequal size, a focal that is not finite or <= 0, a pose that
+ * is not finite, near not finite or < 0, truncation not finite or <= 0, min_alpha outside [0, 1], a misaligned counts_dev or
+ * colour_sum_dev), RF_ERR_UNSUPPORTED (a flag bit other than RF_FUSE_CARVE).  num_views == 0 returns RF_OK without a launch.  (Added
+ * to ABI version 4 compatibly: no existing struct or signature changed.) */
+enum { RF_FUSE_CARVE = 128 };
+int rf_fuse_depth_views(const float* aabb_min, const float* aabb_max, const int32_t* dims, int32_t num_views, const RFCamera* cameras,
+                        const float* depths_dev, const float* alphas_dev, const float* images_dev, float near, float truncation, float min_alpha,
+                        uint32_t flags, float* tsdf_sum_dev, int32_t* counts_dev, float* colour_sum_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

@@ -28,6 +28,13 @@ turn-table of --geometry_fit_views frames by N Adam steps (rf.fit_mesh_to_field_
 clustering cell (two voxels without simplification) from where it started.  It runs after the simplification and before any texture
 bake, so the bake sees the fitted surface.  Off by default: unset, nothing of it is allocated or launched.
 
+--fuse_views N replaces the density iso-surface by the surface the field's VIEWS see: the median depth and accumulated weight of a
+turn-table of N frames are fused into a truncated signed distance volume on the model's grid (rf.fuse_field_views; DESIGN.md section
+26; truncation --fuse_truncation_voxels longest voxel edges) and its zero set is extracted instead; --keep_largest /
+--min_component_nodes then filter the components inside the fused surface, and the simplification, fit and bake options act on the
+fused mesh as on any other.  Unset, the script does exactly what it does without the option.  scripts/fuse_mesh.py has the
+remaining options.
+
 --keep_largest / --min_component_nodes drop the detached shells of floaters: the connected components (26-connectivity) of the nodes
 whose own density exceeds the iso level are filtered in memory before the extraction (thr3ed_atom_amd.components); the checkpoint is
 not touched.
@@ -68,6 +75,8 @@ import thr3ed_atom_amd as rf  # noqa: E402
 @click.option("--texture_fit_iterations", type=click.IntRange(min=0), default=0, required=False, help="with --texture_views: then fit the texture to those renders by this many Adam steps")
 @click.option("--geometry_fit_iterations", type=click.IntRange(min=0), default=0, required=False, help="fit the vertices to the field's depth and alpha renders by this many Adam steps")
 @click.option("--geometry_fit_views", type=click.IntRange(min=2), default=42, required=False, help="with --geometry_fit_iterations: frames of the turn-table the fit looks from")
+@click.option("--fuse_views", type=click.IntRange(min=1), default=None, required=False, help="extract the surface fused from this many turn-table views of the field instead of the density iso-surface")
+@click.option("--fuse_truncation_voxels", type=click.FloatRange(min=0.0, min_open=True), default=3.0, required=False, help="with --fuse_views: truncation distance in (longest) voxel edges")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -87,12 +96,25 @@ def main(**kwargs) -> None:
     iso = config["iso_level"]
     if iso is None:
         iso = math.log(2.0) / min(grid._voxel_size)
-    if filtering:
+    source = grid  # what is meshed, and at which level
+    if config["fuse_views"] is not None:
+        from thr3ed_atom_amd.fusion import default_truncation
+
+        intr = (extra or {}).get("camera_intrinsics", rf.CameraIntrinsics(800, 800, 1111.111))
+        poses = rf.get_thre360_animation_poses((extra or {}).get("hemispherical_radius", 4.0311), 60.0, config["fuse_views"] + 1)  # (the path drops its last frame)
+        truncation = default_truncation([r[0] for r in grid.aabb], [r[1] for r in grid.aabb], grid.grid_dims, config["fuse_truncation_voxels"])
+        volume = rf.fuse_field_views(model, poses, intr, truncation=truncation)
+        source, iso = volume.to_voxel_grid(), 0.0
+        print(f"fused {len(poses)} views of {intr[0]}x{intr[1]} (truncation {truncation:.6g}): {int((volume.observed > 0).sum())} of {volume.tsdf.numel()} nodes observed")
+        if filtering:
+            stats = rf.remove_small_components(source, 0.0, 26, min_nodes=config["min_component_nodes"], keep_largest=config["keep_largest"], fill_density=-1.0)
+            print(f"connected components inside the fused surface: {stats.components}, removed {stats.removed_components} ({stats.removed_nodes} nodes; {stats.kept_nodes} kept)")
+    elif filtering:
         stats = rf.remove_small_components(grid, iso, 26, min_nodes=config["min_component_nodes"], keep_largest=config["keep_largest"], fill_density=config["fill_density"])
         print(f"connected components above the iso level: {stats.components}, removed {stats.removed_components} ({stats.removed_nodes} nodes; {stats.kept_nodes} kept)")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    mesh = rf.extract_mesh(grid, iso, subdivisions=config["subdivisions"])
+    mesh = rf.extract_mesh(source, iso, subdivisions=config["subdivisions"])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     extracted, summary = (len(mesh.vertices), len(mesh.faces)), ""

@@ -51,6 +51,7 @@ from .texture import TextureBake, ViewBake, bake_texture, bake_texture_from_fiel
 from .mesh_raster import MeshRender, evaluate_mesh_against_field, read_obj, render_mesh  # noqa: F401
 from .texture_fit import MeshTextureSampler, TextureFit, fit_texture, fit_texture_to_field_views  # noqa: F401
 from .mesh_fit import MeshFit, MeshGeometryRenderer, fit_mesh_to_field_views, fit_mesh_to_views  # noqa: F401
+from .fusion import FusedVolume, fuse_depth_views, fuse_field_views  # noqa: F401
 from .ops import distortion_loss, render_geometry, total_variation  # noqa: F401
 from .metrics import ssim  # noqa: F401
 from .trainers import evaluate_sh_vox_grid_vol_mod_with_posed_images  # noqa: F401

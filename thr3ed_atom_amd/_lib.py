@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -40,6 +40,8 @@ RASTER_MAX_EDGE, RASTER_LANE_BOX = 16384, 8  # kMaxImageEdge, kLaneBox of csrc/m
 TEXTURE_VIEWS_TWO_SIDED = 64  # RF_TEXTURE_VIEWS_TWO_SIDED
 TEXTURE_VIEWS_MAX_VIEWS, TEXTURE_VIEWS_MAX_COS_POWER = 16, 8  # kMaxViews, kMaxCosPower of csrc/texture_views_kernels.hip: views per rf_texture_project_views call
 TEXTURE_FIT_LONG_SEGMENT, TEXTURE_NO_TAP = 16, 0xFFFF  # kLongSegment, kNoTap of csrc/texture_fit_kernels.hip: longer segments of rf_texture_sample_backward go to the wavefront
+FUSE_CARVE = 128  # RF_FUSE_CARVE
+FUSE_MAX_VIEWS, FUSE_MAX_DIM = 16, 4096  # kMaxViews, kMaxDim of csrc/fusion_kernels.hip: views per rf_fuse_depth_views call, nodes per axis
 MESH_FIT_LONG_SEGMENT = 16  # kLongSegment of csrc/mesh_fit_kernels.hip: longer segments of rf_mesh_geometry_backward_gather go to the wavefront
 SSIM_TILE = (16, 32)  # map rows x columns per workgroup of rf_ssim_forward (image rows x columns of rf_ssim_backward)
 STEP_FORWARD = 1
@@ -118,6 +120,7 @@ EXPORTED_SYMBOLS = [
     "rf_mesh_raster_coverage",
     "rf_mesh_geometry_backward_pixels",
     "rf_mesh_geometry_backward_gather",
+    "rf_fuse_depth_views",
 ]
 
 
@@ -410,6 +413,8 @@ def load() -> C.CDLL:
     lib.rf_mesh_raster_coverage.argtypes = [C.POINTER(RFCamera), vp, i64, vp, i64, vp, u32, vp, vp, vp, vp]
     lib.rf_mesh_geometry_backward_pixels.argtypes = [C.POINTER(RFCamera), vp, i64, vp, i64, vp, vp, vp, vp, u32, vp, vp, vp]
     lib.rf_mesh_geometry_backward_gather.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, u32, vp, vp, vp, vp]
+    # TSDF fusion of posed depth views (csrc/fusion_kernels.hip)
+    lib.rf_fuse_depth_views.argtypes = [fp, fp, i32p, i32, C.POINTER(RFCamera), vp, vp, vp, f32, f32, f32, u32, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
             getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int
