@@ -819,8 +819,8 @@ int rf_texture_sample_backward(const float* grad_colour_dev, int64_t num_pixels,
                                int64_t num_entries, int32_t texture_height, int32_t texture_width, int32_t long_segment, uint32_t flags,
                                float* grad_texture_dev, int32_t* status_dev, void* stream);
 
-/* ---- geometry gradients of the mesh render (csrc/mesh_fit_kernels.hip, which includes csrc/mesh_raster_kernels.hip for its
- * device functions with RF_MESH_RASTER_DEVICE_ONLY defined; DESIGN.md section 25;
+/* ---- geometry gradients of the mesh render (csrc/mesh_fit_kernels.hip over the rasteriser's device functions in
+ * csrc/mesh_raster.h; DESIGN.md section 25;
  * thr3ed_atom_amd/mesh_fit.py sorts the hit pixels, builds the corner lists and runs the optimiser) -------------------------------
  * Two images per view that are differentiable with respect to vertices_dev, in the rasteriser's own quantities (d, p_k = v_k - o,
  * e_k, s, w_k = e_k / s, z as defined above, computed by the device functions the visibility and shade kernels call):

@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+from tests import csrc_text
 from thr3ed_atom_amd import _lib
 
 OK, NULL, SHAPE, UNSUPPORTED = 0, -1, -2, -3
@@ -30,18 +31,19 @@ def test_entry_point(lib):
             "                        const float* depths_dev, const float* alphas_dev, const float* images_dev, float near, float truncation, float min_alpha,\n"
             "                        uint32_t flags, float* tsdf_sum_dev, int32_t* counts_dev, float* colour_sum_dev, void* stream);") in header
     assert len(lib.rf_fuse_depth_views.argtypes) == 16
-    source = open(os.path.join(_lib.CSRC_DIR, UNIT)).read()
+    source = csrc_text.unit_code(UNIT)  # the unit together with its private header
     assert [int(v) for v in re.findall(r"constexpr int kMaxViews = (\d+);", source)] == [_lib.FUSE_MAX_VIEWS]
-    assert [int(v) for v in re.findall(r"constexpr int kMaxDim = (\d+);", source)] == [_lib.FUSE_MAX_DIM]
+    assert [int(v) for v in re.findall(r"constexpr int kMaxViews = (\d+);", csrc_text.code("view_camera.h"))] == [_lib.FUSE_MAX_VIEWS]
+    assert [int(v) for v in re.findall(r"constexpr int kMaxDim = (\d+);", csrc_text.code(UNIT))] == [_lib.FUSE_MAX_DIM]
 
 
 def test_the_unit_has_no_atomics_no_lds_and_no_assembly():
-    source = open(os.path.join(_lib.CSRC_DIR, UNIT)).read()
-    code = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", source, flags=re.S))
+    code = csrc_text.unit_code(UNIT)  # the unit together with its private header
     assert "__global__" in code
     for word in ("atomic", "__shared__", "asm", "__syncthreads", "__builtin_amdgcn"):
         assert word not in code, word
-    assert re.findall(r'#include\s+"([^"]+)"', code) == ["rf_device.h"]
+    assert csrc_text.includes(UNIT) == ["view_camera.h"] and csrc_text.includes("view_camera.h") == ["rf_device.h"]
+    assert os.path.join(_lib.CSRC_DIR, "view_camera.h") in _lib.build_inputs()
 
 
 def camera(height=8, width=8, focal=10.0, pose=(1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 4)):

@@ -7,6 +7,7 @@ import re
 
 import pytest
 
+from tests import csrc_text
 from thr3ed_atom_amd import _lib
 
 OK, NULL, SHAPE, UNSUPPORTED = 0, -1, -2, -3
@@ -30,20 +31,23 @@ def test_entry_points(lib):
     assert "#define RF_ABI_VERSION 4" in header
     for name in NEW:
         assert f"int {name}(const " in header
-    source = open(os.path.join(_lib.CSRC_DIR, "mesh_fit_kernels.hip")).read()
-    assert re.findall(r"constexpr int kLongSegment = (\d+);", source) == [str(_lib.MESH_FIT_LONG_SEGMENT)]
-    # gather form: no atomics, no memset, no LDS, no inline assembly in the new unit
-    code = re.sub(r"//.*", "", source)
-    assert "atomic" not in code.lower() and "hipMemset" not in code and "__shared__" not in code and "asm" not in code
-    # the rasteriser's quantities are the rasteriser's: the unit includes its device functions and restates neither the ray's edge values
-    # nor the face set-up; the raster unit leaves its kernels and entry points out of that inclusion
-    assert "#define RF_MESH_RASTER_DEVICE_ONLY" in code and '#include "mesh_raster_kernels.hip"' in code
+    code = csrc_text.code("mesh_fit_kernels.hip")
+    assert re.findall(r"constexpr int kLongSegment = (\d+);", code) == [str(_lib.MESH_FIT_LONG_SEGMENT)]
+    # gather form: no atomics, no memset, no LDS, no inline assembly in the unit and the private headers it includes, but for the one
+    # atomic of the header that is the visibility pass's own (tests/test_mesh_raster_abi.py) -- the header has none
+    whole = csrc_text.unit_code("mesh_fit_kernels.hip")
+    assert csrc_text.private_headers("mesh_fit_kernels.hip") == ["mesh_raster.h", "view_camera.h", "segment_sum.h"]
+    assert "atomic" not in whole.lower() and "hipMemset" not in whole and "__shared__" not in whole and "asm" not in whole
+    # the rasteriser's quantities are the rasteriser's: the unit includes the header of its device functions and restates neither the
+    # ray's edge values nor the face set-up; no unit is included by anything, and the raster unit keeps its kernels and entry points
+    assert csrc_text.includes("mesh_fit_kernels.hip") == ["mesh_raster.h", "segment_sum.h"] and "#define" not in code and "#if" not in whole
     assert "raster_edges(" in code and "raster_hit(" in code and "raster_face(" in code and "load_face(" in code
-    assert "float raster_edges(" not in code and "RasterFace raster_face(" not in code and "f.c[k]" not in code
-    raster = re.sub(r"//.*", "", open(os.path.join(_lib.CSRC_DIR, "mesh_raster_kernels.hip")).read())
-    assert raster.count("#ifndef RF_MESH_RASTER_DEVICE_ONLY") == raster.count("#endif") == 4 and raster.count("float raster_edges(") == 1
-    guarded = "".join(part.split("#endif")[0] for part in raster.split("#ifndef RF_MESH_RASTER_DEVICE_ONLY")[1:])
-    assert guarded.count("__global__") == raster.count("__global__") == 3 and 'extern "C"' in guarded and "int rf_mesh_raster_taps(" in guarded
+    assert "float raster_edges(" not in code and "RasterFace raster_face(" not in code and "RasterHit raster_hit(" not in code and "bool load_face(" not in code
+    assert "f.c[k]" not in code and "cross_v" not in code and code.count("cross3(") == 3
+    header, raster = csrc_text.code("mesh_raster.h"), csrc_text.code("mesh_raster_kernels.hip")
+    assert header.count("float raster_edges(") == 1 and header.count("RasterFace raster_face(") == 1 and header.count("void cross3(") == 1
+    assert "__global__" not in header and 'extern "C"' not in header and "#if" not in raster and "#define" not in raster
+    assert raster.count("__global__") == 3 and 'extern "C"' in raster and "int rf_mesh_raster_taps(" in raster and "float raster_edges(" not in raster
 
 
 def camera(height=8, width=12, focal=10.0):

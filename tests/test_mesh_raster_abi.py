@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+from tests import csrc_text
 from thr3ed_atom_amd import _lib
 
 OK, NULL, SHAPE, UNSUPPORTED = 0, -1, -2, -3
@@ -30,16 +31,24 @@ def test_entry_points(lib):
     assert "int rf_mesh_raster_shade(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces," in header
     assert f"enum {{ RF_RASTER_CULL_BACKFACES = {_lib.RASTER_CULL_BACKFACES} }};" in header
     assert _lib.RASTER_CULL_BACKFACES not in (_lib.FLAG_WHITE_BKGD, _lib.FLAG_RENDER_DIFFUSE, _lib.FLAG_AABB_SAMPLING, _lib.FLAG_OCCUPANCY_SKIP, _lib.FLAG_JITTER_KEYED)
-    # the limits the binding checks are the ones the unit is compiled with
-    source = open(os.path.join(_lib.CSRC_DIR, "mesh_raster_kernels.hip")).read()
-    assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", source) == [str(_lib.RASTER_MAX_EDGE)]
-    assert re.findall(r"constexpr int kLaneBox = (\d+);", source) == [str(_lib.RASTER_LANE_BOX)]
-    code = re.sub(r"//.*", "", source)
+    # the limits the binding checks are the ones the unit is compiled with (they live in the private headers the unit includes)
+    assert csrc_text.private_headers("mesh_raster_kernels.hip") == ["mesh_raster.h", "view_camera.h"]
+    assert os.path.join(_lib.CSRC_DIR, "mesh_raster.h") in _lib.build_inputs() and os.path.join(_lib.CSRC_DIR, "view_camera.h") in _lib.build_inputs()
+    assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", csrc_text.code("view_camera.h")) == [str(_lib.RASTER_MAX_EDGE)]
+    assert re.findall(r"constexpr int kLaneBox = (\d+);", csrc_text.code("mesh_raster.h")) == [str(_lib.RASTER_LANE_BOX)]
+    code = csrc_text.unit_code("mesh_raster_kernels.hip")  # the unit together with its private headers
+    assert len(re.findall(r"constexpr int kMaxImageEdge = ", code)) == len(re.findall(r"constexpr int kLaneBox = ", code)) == 1
     # the ray is cast_rays' own, the only atomic is the 64-bit minimum of the visibility pass, and nothing needs LDS or a barrier
     assert "pixel_ray(" in code and "-ffp-contract=off" in _lib.HIPCC_FLAGS
     assert re.findall(r"__hip_atomic_fetch_\w+|atomic[A-Z]\w+", code) == ["__hip_atomic_fetch_min"]
-    shade = code[code.index("void mesh_raster_shade_kernel"):code.index("int check_raster")]
-    assert "atomic" not in shade.lower() and "raster_hit(" in shade and "raster_face(" in shade
+    # the shade kernel has no atomic and takes its hit from raster_hit and raster_face, through winning_hit of the header
+    unit = csrc_text.code("mesh_raster_kernels.hip")
+    shade = unit[unit.index("void mesh_raster_shade_kernel"):unit.index("void mesh_raster_taps_kernel")]
+    assert "atomic" not in shade.lower() and "winning_hit(" in shade and "texel_taps(" in shade and "bilinear_blend(" in shade
+    header = csrc_text.code("mesh_raster.h")
+    winning_hit = header[header.index("bool winning_hit("):header.index("BilinearTaps texel_taps(")]
+    assert "raster_hit(" in winning_hit and "raster_face(" in winning_hit and "load_face(" in winning_hit and "winning_key(" in winning_hit and "atomic" not in header.lower()
+    assert "int check_raster(" in header and "check_raster(" in unit and "int check_raster(" not in unit
     assert "__shared__" not in code and "__syncthreads" not in code and "hipMemset" not in code
 
 

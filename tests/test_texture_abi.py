@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+from tests import csrc_text
 from thr3ed_atom_amd import _lib
 
 OK, NULL, SHAPE, UNSUPPORTED = 0, -1, -2, -3
@@ -30,7 +31,7 @@ def test_entry_point(lib):
     source = open(os.path.join(_lib.CSRC_DIR, "texture_kernels.hip")).read()
     assert re.findall(r"constexpr int kMinPatch = (\d+), kMaxPatch = (\d+);", source) == [(str(_lib.TEXTURE_MIN_PATCH), str(_lib.TEXTURE_MAX_PATCH))]
     assert re.findall(r"constexpr int kMaxSamples = (\d+);", source) == [str(_lib.TEXTURE_MAX_SAMPLES)]
-    assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", source) == [str(_lib.TEXTURE_MAX_EDGE)]
+    assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", csrc_text.unit_code("texture_kernels.hip")) == [str(_lib.TEXTURE_MAX_EDGE)]  # (view_camera.h's)
     assert "const int block = patch + 4;" in source and _lib.TEXTURE_GUTTER == 4
     # one lane per texel, every texel written once: no atomics in the unit, and the addressing comes from the shared header
     code = re.sub(r"//.*", "", source)

@@ -7,6 +7,7 @@ import re
 
 import pytest
 
+from tests import csrc_text
 from thr3ed_atom_amd import _lib
 
 OK, NULL, SHAPE, UNSUPPORTED = 0, -1, -2, -3
@@ -34,15 +35,22 @@ def test_entry_points(lib):
         assert prototype in header
     assert "uint16_t x0, x1, y0, y1;" in header and "} RFTextureTap; /* 16 bytes */" in header and "} RFTextureTapEntry; /* 8 bytes */" in header
     # the limits the binding names are the ones the unit is compiled with
-    source = open(os.path.join(_lib.CSRC_DIR, "texture_fit_kernels.hip")).read()
+    source = csrc_text.code("texture_fit_kernels.hip")
     assert re.findall(r"constexpr int kLongSegment = (\d+);", source) == [str(_lib.TEXTURE_FIT_LONG_SEGMENT)]
     assert re.findall(r"constexpr unsigned int kNoTap = 0x([0-9a-f]+)u;", source) == [format(_lib.TEXTURE_NO_TAP, "x")]
-    assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", source) == [str(_lib.RASTER_MAX_EDGE)] and _lib.TEXTURE_NO_TAP > _lib.RASTER_MAX_EDGE
-    # gather form: no atomics, no memset, no LDS in the new unit; both raster kernels go through the two shared device functions
-    code = re.sub(r"//.*", "", source)
+    code = csrc_text.unit_code("texture_fit_kernels.hip")  # the unit together with its private headers
+    assert csrc_text.private_headers("texture_fit_kernels.hip") == ["segment_sum.h", "view_camera.h"]
+    assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", code) == [str(_lib.RASTER_MAX_EDGE)] and _lib.TEXTURE_NO_TAP > _lib.RASTER_MAX_EDGE
+    # gather form: no atomics, no memset, no LDS in the unit and its headers; both raster kernels go through the two shared device
+    # functions, and the fetch of texture_sample_kernel is the shade kernel's: one bilinear_blend
     assert "atomic" not in code.lower() and "hipMemset" not in code and "__shared__" not in code
-    raster = re.sub(r"//.*", "", open(os.path.join(_lib.CSRC_DIR, "mesh_raster_kernels.hip")).read())
-    assert raster.count("winning_hit(") == 4 and raster.count("texel_taps(") == 3  # one definition (winning_hit: and its declaration), two callers each
+    raster, header = csrc_text.code("mesh_raster_kernels.hip"), csrc_text.code("mesh_raster.h")
+    assert raster.count("winning_hit(") == 2 and raster.count("texel_taps(") == 2  # two callers each ...
+    assert header.count("winning_hit(") == 1 and header.count("texel_taps(") == 1  # ... of one definition, with no separate declaration
+    assert header.index("bool winning_hit(") < header.index("BilinearTaps texel_taps(") and "bilinear_taps(" in header[header.index("BilinearTaps texel_taps("):]
+    assert source.count("bilinear_blend(") == 1 and raster.count("bilinear_blend(") == 1 and csrc_text.code("view_camera.h").count("float bilinear_blend(") == 1
+    for text in (source, raster):
+        assert "top" not in text and "bot" not in text  # (neither restates the blend)
 
 
 def camera(height=8, width=12, focal=10.0):

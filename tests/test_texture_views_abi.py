@@ -6,6 +6,7 @@ import re
 
 import pytest
 
+from tests import csrc_text
 from thr3ed_atom_amd import _lib
 
 OK, NULL, SHAPE, UNSUPPORTED = 0, -1, -2, -3
@@ -31,17 +32,22 @@ def test_entry_point(lib):
     assert _lib.TEXTURE_VIEWS_TWO_SIDED not in (_lib.FLAG_WHITE_BKGD, _lib.FLAG_RENDER_DIFFUSE, _lib.FLAG_AABB_SAMPLING, _lib.FLAG_OCCUPANCY_SKIP,
                                                 _lib.FLAG_JITTER_KEYED, _lib.RASTER_CULL_BACKFACES)
     # the limits the binding checks are the ones the unit is compiled with
-    source = open(os.path.join(_lib.CSRC_DIR, "texture_views_kernels.hip")).read()
+    source = csrc_text.unit_code("texture_views_kernels.hip")  # the unit together with its private headers
+    assert csrc_text.private_headers("texture_views_kernels.hip") == ["texture_atlas.h", "view_camera.h"]
+    assert os.path.join(_lib.CSRC_DIR, "view_camera.h") in _lib.build_inputs()
     assert re.findall(r"constexpr int kMaxViews = (\d+);", source) == [str(_lib.TEXTURE_VIEWS_MAX_VIEWS)]
+    assert re.findall(r"constexpr int kMaxViews = (\d+);", csrc_text.code("view_camera.h")) == [str(_lib.TEXTURE_VIEWS_MAX_VIEWS)]
     assert re.findall(r"constexpr int kMaxCosPower = (\d+);", source) == [str(_lib.TEXTURE_VIEWS_MAX_COS_POWER)]
     assert re.findall(r"constexpr int kMinPatch = (\d+), kMaxPatch = (\d+);", source) == [(str(_lib.TEXTURE_MIN_PATCH), str(_lib.TEXTURE_MAX_PATCH))]
     assert re.findall(r"constexpr int kMaxImageEdge = (\d+);", source) == [str(_lib.TEXTURE_MAX_EDGE)]
     assert C.sizeof(_lib.RFCamera) == 60  # 16 of them travel in the kernel's argument struct
     # one lane per texel, load-add-store: no atomics and no memset in the unit; the atlas map is the shared one in both units
-    code = re.sub(r"//.*", "", source)
+    code = source
     assert "atomic" not in code.lower() and "hipMemset" not in code
-    bake = re.sub(r"//.*", "", open(os.path.join(_lib.CSRC_DIR, "texture_kernels.hip")).read())
-    for unit in (code, bake):
+    own = csrc_text.code("texture_views_kernels.hip")
+    assert "bilinear_taps(" in own and "bilinear_blend(" in own and "floorf" not in own and "fill_view_cameras(" in own and "view_cameras_ok(" in own
+    bake = csrc_text.code("texture_kernels.hip")
+    for unit in (own, bake):
         assert '#include "texture_atlas.h"' in unit
         for helper in ("atlas_texel(", "atlas_face(", "atlas_point("):
             assert helper in unit

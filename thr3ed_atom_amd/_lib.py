@@ -34,14 +34,14 @@ CONNECTIVITIES = (6, 18, 26)  # rf_label_components
 MESH_PLACEMENTS = {"quadric": 0, "mean": 1}  # RF_MESH_PLACEMENT_*
 MESH_MAX_CELLS = 1 << 20  # per axis (rf_mesh_cluster_keys)
 MESH_CLUSTER_GROUP, MESH_CLUSTERS_PER_BLOCK, MESH_LONG_SEGMENT = 16, 16, 256  # kClusterGroup, kClustersPerBlock, kLongSegment of csrc/mesh_simplify_kernels.hip
-TEXTURE_MIN_PATCH, TEXTURE_MAX_PATCH, TEXTURE_GUTTER, TEXTURE_MAX_SAMPLES, TEXTURE_MAX_EDGE = 2, 64, 4, 256, 16384  # rf_texture_bake (csrc/texture_kernels.hip): block edge = patch + gutter
+TEXTURE_MIN_PATCH, TEXTURE_MAX_PATCH, TEXTURE_GUTTER, TEXTURE_MAX_SAMPLES, TEXTURE_MAX_EDGE = 2, 64, 4, 256, 16384  # rf_texture_bake (csrc/texture_kernels.hip; the edge: kMaxImageEdge of csrc/view_camera.h): block edge = patch + gutter
 RASTER_CULL_BACKFACES = 32  # RF_RASTER_CULL_BACKFACES
-RASTER_MAX_EDGE, RASTER_LANE_BOX = 16384, 8  # kMaxImageEdge, kLaneBox of csrc/mesh_raster_kernels.hip
+RASTER_MAX_EDGE, RASTER_LANE_BOX = 16384, 8  # kMaxImageEdge of csrc/view_camera.h, kLaneBox of csrc/mesh_raster.h
 TEXTURE_VIEWS_TWO_SIDED = 64  # RF_TEXTURE_VIEWS_TWO_SIDED
-TEXTURE_VIEWS_MAX_VIEWS, TEXTURE_VIEWS_MAX_COS_POWER = 16, 8  # kMaxViews, kMaxCosPower of csrc/texture_views_kernels.hip: views per rf_texture_project_views call
+TEXTURE_VIEWS_MAX_VIEWS, TEXTURE_VIEWS_MAX_COS_POWER = 16, 8  # kMaxViews of csrc/view_camera.h, kMaxCosPower of csrc/texture_views_kernels.hip: views per rf_texture_project_views call
 TEXTURE_FIT_LONG_SEGMENT, TEXTURE_NO_TAP = 16, 0xFFFF  # kLongSegment, kNoTap of csrc/texture_fit_kernels.hip: longer segments of rf_texture_sample_backward go to the wavefront
 FUSE_CARVE = 128  # RF_FUSE_CARVE
-FUSE_MAX_VIEWS, FUSE_MAX_DIM = 16, 4096  # kMaxViews, kMaxDim of csrc/fusion_kernels.hip: views per rf_fuse_depth_views call, nodes per axis
+FUSE_MAX_VIEWS, FUSE_MAX_DIM = 16, 4096  # kMaxViews of csrc/view_camera.h, kMaxDim of csrc/fusion_kernels.hip: views per rf_fuse_depth_views call, nodes per axis
 MESH_FIT_LONG_SEGMENT = 16  # kLongSegment of csrc/mesh_fit_kernels.hip: longer segments of rf_mesh_geometry_backward_gather go to the wavefront
 SSIM_TILE = (16, 32)  # map rows x columns per workgroup of rf_ssim_forward (image rows x columns of rf_ssim_backward)
 STEP_FORWARD = 1

@@ -1,6 +1,8 @@
 """How tensors, cameras and meshes cross the C ABI (include/relu_field.h): raw pointers, the stream handle, the RFCamera of a posed
-pinhole camera and the checks every mesh entry point makes before its first launch.  A leaf: it imports the library binding and
-the camera tuples and nothing else of the package, so ``ops``, ``voxels``, ``mesh``, ``texture`` and ``mesh_raster`` can all use it."""
+pinhole camera, the checks every mesh entry point makes before its first launch, the visibility pass and the offsets of a segmented
+sum.  A leaf: it imports the library binding and the camera tuples and nothing else of the package, so ``ops``, ``voxels``, ``mesh``,
+``texture``, ``mesh_raster`` and the two fits can all use it."""
+import ctypes as C
 import math
 from typing import Optional, Tuple
 
@@ -30,6 +32,23 @@ def non_negative(value, name: str) -> float:
     if not (math.isfinite(value) and value >= 0.0):
         raise ValueError(f"{name} must be non-negative and finite, got {value!r}")
     return value
+
+
+def positive(value, name: str) -> float:
+    value = float(value)
+    if not (math.isfinite(value) and value > 0.0):
+        raise ValueError(f"{name} must be positive and finite, got {value!r}")
+    return value
+
+
+def iteration_count(iterations) -> int:
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
+        raise ValueError(f"iterations must be a non-negative integer, got {iterations!r}")
+    return int(iterations)
+
+
+def identity_pose() -> CameraPose:
+    return CameraPose(torch.eye(3), torch.zeros(3, 1))
 
 
 def camera_struct(height, width, focal, rotation, translation) -> "_lib.RFCamera":
@@ -85,3 +104,19 @@ def require_faces_in_range(status: Tensor, num_vertices: int) -> None:
     """the status word a mesh kernel raises when a face indexes outside the vertices (one host read)"""
     if int(status.item()):
         raise ValueError(f"faces index outside [0, {num_vertices})")
+
+
+def raster_visibility(cam: "_lib.RFCamera", vertices: Tensor, faces: Tensor, near: float, flags: int, visibility: Tensor, status: Tensor) -> None:
+    """one view's visibility pass into ``visibility`` (int64 [H, W], overwritten); a face outside the vertices raises ``status``"""
+    visibility.fill_(-1)  # all ones: nothing hit
+    rc = _lib.load().rf_mesh_raster_visibility(C.byref(cam), vertices.data_ptr(), int(vertices.shape[0]), faces.data_ptr(), int(faces.shape[0]), near, flags,
+                                               visibility.data_ptr(), status.data_ptr(), stream(vertices.device))
+    _lib.check(rc, "rf_mesh_raster_visibility")
+
+
+def segment_offsets(keys: Tensor, count: int) -> Tensor:
+    """int64 [count + 1]: where the entries of each key in [0, count) begin once they are sorted by key (``keys`` in any order)"""
+    counts = torch.bincount(keys, minlength=count) if count and keys.numel() else torch.zeros(count, dtype=torch.int64, device=keys.device)
+    offsets = torch.zeros(count + 1, dtype=torch.int64, device=keys.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return offsets

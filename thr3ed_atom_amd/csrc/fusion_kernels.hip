@@ -26,13 +26,11 @@
 // The other natural mapping, 64 consecutive iz per wavefront (coalesced accumulators, up to 64 scattered depth pixels per view), was
 // measured 5.1 x slower on the 256^3 scene and is not kept (profiles/fusion_mapping_ab.md).  The contract fixes
 // only the order of views per node, so the mapping changes no bit.
-#include "rf_device.h"
+#include "view_camera.h"
 
 namespace {
 
 constexpr int kFuseBlock = 256;
-constexpr int kMaxViews = 16;
-constexpr int kMaxImageEdge = 16384;
 constexpr int kMaxDim = 4096;
 
 struct FuseArgs {
@@ -133,14 +131,7 @@ int rf_fuse_depth_views(const float* aabb_min, const float* aabb_max, const int3
     if (!std::isfinite(aabb_max[a] - aabb_min[a])) return RF_ERR_BAD_SHAPE;  // (the extent itself overflows)
   }
   if (num_views < 0 || num_views > kMaxViews) return RF_ERR_BAD_SHAPE;
-  for (int k = 0; k < num_views; ++k) {
-    const RFCamera& cam = cameras[k];
-    if (cam.height < 1 || cam.height > kMaxImageEdge || cam.width < 1 || cam.width > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
-    if (cam.height != cameras[0].height || cam.width != cameras[0].width) return RF_ERR_BAD_SHAPE;
-    if (!std::isfinite(cam.focal) || !(cam.focal > 0.0f)) return RF_ERR_BAD_SHAPE;
-    for (int e = 0; e < 12; ++e)
-      if (!std::isfinite(cam.pose[e])) return RF_ERR_BAD_SHAPE;
-  }
+  if (!view_cameras_ok(cameras, num_views)) return RF_ERR_BAD_SHAPE;
   if (!std::isfinite(near) || !(near >= 0.0f)) return RF_ERR_BAD_SHAPE;
   if (!std::isfinite(truncation) || !(truncation > 0.0f)) return RF_ERR_BAD_SHAPE;
   if (!(min_alpha >= 0.0f) || !(min_alpha <= 1.0f)) return RF_ERR_BAD_SHAPE;
@@ -158,7 +149,7 @@ int rf_fuse_depth_views(const float* aabb_min, const float* aabb_max, const int3
   a.near = near, a.truncation = truncation, a.min_alpha = min_alpha;
   a.carve = (flags & RF_FUSE_CARVE) ? 1 : 0;
   a.tsdf_sum = tsdf_sum_dev, a.counts = (int2*)counts_dev, a.colour_sum = (float4*)colour_sum_dev;
-  for (int k = 0; k < kMaxViews; ++k) a.cams[k] = cameras[k < num_views ? k : 0];  // (the tail is never read; it is not left uninitialised)
+  fill_view_cameras(a.cams, cameras, num_views);
   const dim3 grid((unsigned)((a.lanes + kFuseBlock - 1) / kFuseBlock)), block(kFuseBlock);  // <= 2^28 workgroups
   hipLaunchKernelGGL(fuse_depth_views_kernel, grid, block, 0, (hipStream_t)stream, a);
   return launch_status();

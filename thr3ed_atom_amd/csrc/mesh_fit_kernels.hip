@@ -4,8 +4,8 @@
 // docs/mesh_fit_errors.md the error bound, tests/mesh_fit_model.py the float64 model.
 //
 // Every quantity of the rasteriser -- the pixel ray d, p_k = v_k - o, the edge values e_k, s, w_k, z -- comes from the device functions
-// of mesh_raster_kernels.hip (winning_key, load_face, raster_face, raster_edges, raster_hit), the ones the visibility and shade kernels call: that
-// file is included below for its device functions alone, so the depth image holds rf_mesh_raster_shade's bits.
+// of mesh_raster.h (winning_key, load_face, raster_face, raster_edges, raster_hit), the ones the visibility and shade kernels call, so
+// the depth image holds rf_mesh_raster_shade's bits.
 //
 // Coverage.  The edge-crossing rule of nvdiffrast (Laine et al. 2020) restricted to hit-against-miss pixel pairs.  For a hit pixel a
 // with winning face F and a 4-neighbour b inside the image that nothing hit: sigma = sign(s(a)); over the k with sigma e_k(b) < 0,
@@ -20,12 +20,11 @@
 // G = [tau > 1/2][A(b) < 1] grad_coverage(b) + [tau < 1/2][A(a) > 0] grad_coverage(a): a saturated pixel, decided from the SAVED
 // coverage image, passes nothing, and neither does tau = 1/2 exactly.  Miss pixels write nothing.
 //
-// Backward, stage 2.  Two segmented sums in gather form with the kernel below: per face over its hit pixels (the host sorts them by
-// face, stably), then per vertex over its (face, corner) slots.  A short segment is summed by its lane in entry order; a longer one
-// by the whole wavefront (ballot hand-off, lane l takes entries l, l + 64, ..., a fixed shuffle tree), as
-// texture_sample_backward_kernel does.  No atomics, no LDS, no barrier; every output row is written, 0 for an empty segment.
-#define RF_MESH_RASTER_DEVICE_ONLY
-#include "mesh_raster_kernels.hip"
+// Backward, stage 2.  Two segmented sums in gather form with segment_sum of segment_sum.h, which texture_sample_backward_kernel
+// instantiates too: per face over its hit pixels (the host sorts them by face, stably), then per vertex over its (face, corner)
+// slots.  No atomics, no LDS, no barrier; every output row is written, 0 for an empty segment.
+#include "mesh_raster.h"
+#include "segment_sum.h"
 
 namespace {
 
@@ -110,12 +109,6 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_coverage_kernel(Rast
   face_ids[pix] = id;
 }
 
-__device__ __forceinline__ void cross_v(const float (&a)[3], const float (&b)[3], float (&out)[3]) {
-  out[0] = a[1] * b[2] - a[2] * b[1];
-  out[1] = a[2] * b[0] - a[0] * b[2];
-  out[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 __global__ __launch_bounds__(kRasterBlock) void mesh_geometry_backward_pixels_kernel(RasterArgs a, const int* __restrict__ face_ids, const float* __restrict__ coverage,
                                                                                      const float* __restrict__ grad_depth, const float* __restrict__ grad_coverage,
                                                                                      float* __restrict__ records, int* status) {
@@ -148,7 +141,7 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_geometry_backward_pixels_ke
     float u1[3], u2[3], n[3];
 #pragma unroll
     for (int x = 0; x < 3; ++x) u1[x] = v[1][x] - v[0][x], u2[x] = v[2][x] - v[0][x];
-    cross_v(u1, u2, n);
+    cross3(u1, u2, n);
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const float c = gz * ((ea[k] / sa) / sa);
@@ -182,8 +175,8 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_geometry_backward_pixels_ke
       p1[x] = c.k == 0 ? p[1][x] : c.k == 1 ? p[2][x] : p[0][x];
       p2[x] = c.k == 0 ? p[2][x] : c.k == 1 ? p[0][x] : p[1][x];
     }
-    cross_v(p2, D, g1);  // de_k/dp_k1 = p_k2 x d
-    cross_v(D, p1, g2);  // de_k/dp_k2 = d x p_k1
+    cross3(p2, D, g1);  // de_k/dp_k1 = p_k2 x d
+    cross3(D, p1, g2);  // de_k/dp_k2 = d x p_k1
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const bool first = k == (c.k + 1) % 3, second = k == (c.k + 2) % 3;
@@ -210,47 +203,21 @@ __device__ __forceinline__ void add_row(const float* __restrict__ rows, long lon
   for (int c = 0; c < C; ++c) acc[c] = acc[c] + g[c];
 }
 
+// what segment_sum adds for entry e of the list
+template <int C>
+struct AddRow {
+  const float* rows;
+  long long num_rows;
+  const int* entries;
+  int* status;
+  __device__ __forceinline__ void operator()(long long e, float (&acc)[C]) const { add_row<C>(rows, num_rows, entries[e], acc, status); }
+};
+
 template <int C>
 __global__ __launch_bounds__(kRasterBlock) void segment_sum_kernel(const float* __restrict__ rows, long long num_rows, const int* __restrict__ entries, long long E,
                                                                    const long long* __restrict__ offsets, long long segments, int long_segment,
                                                                    float* __restrict__ out, int* status) {
-  const long long k = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63);
-  // (no lane returns early: the ballot loop below needs the whole wavefront)
-  long long lo = 0, hi = 0;
-  if (k < segments) {  // (clamped: a malformed offset list reads no entry outside [0, E))
-    lo = min(max(offsets[k], 0ll), E);
-    hi = min(max(offsets[k + 1], lo), E);
-  }
-  const bool is_long = hi - lo > (long long)long_segment;
-  if (k < segments && !is_long) {
-    float acc[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = 0.0f;
-    for (long long e = lo; e < hi; ++e) add_row<C>(rows, num_rows, entries[e], acc, status);
-#pragma unroll
-    for (int c = 0; c < C; ++c) out[C * k + c] = acc[c];
-  }
-  unsigned long long todo = __ballot(is_long);
-  while (todo) {  // (wave-uniform)
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const long long slo = __shfl(lo, src, 64), shi = __shfl(hi, src, 64);
-    float acc[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) acc[c] = 0.0f;
-    for (long long e = slo + lane; e < shi; e += 64) add_row<C>(rows, num_rows, entries[e], acc, status);
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) acc[c] = acc[c] + __shfl_down(acc[c], step, 64);  // (lanes past 63 - step read their own value: only lane 0 is used)
-    }
-    if (lane == 0) {
-      const long long dst = k + src;  // (lane 0's segment is the first of the wavefront's 64)
-#pragma unroll
-      for (int c = 0; c < C; ++c) out[C * dst + c] = acc[c];
-    }
-  }
+  segment_sum<C, kRasterBlock>(offsets, E, segments, long_segment, out, AddRow<C>{rows, num_rows, entries, status});
 }
 
 }  // namespace

@@ -1,24 +1,8 @@
-// mesh_raster_kernels.hip -- a rasteriser for exported triangle meshes (rf_mesh_raster_visibility / rf_mesh_raster_shade of
-// relu_field.h): what thr3ed_atom_amd/mesh_raster.py is built on.  DESIGN.md section 22 has the contract, docs/mesh_raster_errors.md
-// the error bound, tests/mesh_raster_model.py the float64 model.
-//
-// The ray.  Pixel (i, j) has exactly the ray cast_rays gives it: o = t, d = pixel_ray(i, j) of rf_device.h (the same float32
-// operations in the same order).  With p_k = v_k - o the edge values of the ray are the triple products e0 = d . (p1 x p2),
-// e1 = d . (p2 x p0), e2 = d . (p0 x p1); s = (e0 + e1) + e2 = d . ((v1 - v0) x (v2 - v0)) up to rounding.
-//
-// Watertight edges.  Every component of a cross product is ONE subtraction of two products and the library is built with
-// -ffp-contract=off, so p_a x p_b = -(p_b x p_a) holds bit for bit, and so does the dot product with d.  The kernels do not lean on
-// the compiler keeping that symmetry through two differently ordered call sites: every edge is evaluated from its LOWER to its
-// HIGHER vertex index and the sign is flipped afterwards when the face runs the other way.  Two faces that share an edge therefore
-// see e and -e, never e and -e(1 + ulp): a ray is on the inner side of exactly one of them, or exactly on the edge of both -- no
-// crack, no double cover away from the edge, and no fill-rule table.
-//
-// Coverage.  A ray hits when all three e are >= 0 or all three are <= 0, and s != 0 (edges inclusive; zero-area and edge-on faces
-// have s == 0 and are never drawn).  Mesh.faces has (v1 - v0) x (v2 - v0) pointing OUT of the solid, so a face seen from outside has
-// s < 0: under RF_RASTER_CULL_BACKFACES only s < 0 counts.  w_k = e_k / s.  z_k = the camera depth of corner k, the component of p_k
-// along -R[:, 2]; z = z0 + (w1 (z1 - z0) + w2 (z2 - z0)) -- sum_k w_k z_k anchored at corner 0, so that a face at one camera depth has
-// that depth exactly -- is the ray parameter of the hit, the quantity RenderOut.depth holds.  A face with any z_k < near is not drawn
-// at all (the documented rule; not a clip).
+// mesh_raster_kernels.hip -- a rasteriser for exported triangle meshes (rf_mesh_raster_visibility / rf_mesh_raster_shade /
+// rf_mesh_raster_taps of relu_field.h): what thr3ed_atom_amd/mesh_raster.py is built on.  DESIGN.md section 22 has the contract,
+// docs/mesh_raster_errors.md the error bound, tests/mesh_raster_model.py the float64 model.  The ray, the watertight edge values, the
+// coverage rule and the depth are the device functions of mesh_raster.h, which csrc/mesh_fit_kernels.hip
+// includes too.  A face with any z_k < near is not drawn at all (the documented rule; not a clip).
 //
 // The visibility pass.  One uint64 per pixel, float_bits(z) << 32 | face, all ones = nothing; device-scope 64-bit atomicMin without
 // a return value.  z >= 0, so its bits order like the number; the minimum does not depend on the order of arrival and the lower
@@ -36,121 +20,13 @@
 // sum_k w_k colour_k of the vertex colours.  Pixels without a hit get the background, depth 0 and face id -1.
 //
 // The taps pass (rf_mesh_raster_taps).  One lane per pixel, the shade pass up to its fetch: winning_hit and
-// texel_taps are the two device functions both kernels call, so a tap record holds the bits the shade kernel fetches through.
-// thr3ed_atom_amd/texture_fit.py turns the records of many views into the sparse matrix whose adjoint csrc/texture_fit_kernels.hip sums.
-//
-// csrc/mesh_fit_kernels.hip needs the device functions of this file -- the face set-up, the edge values, the
-// coverage rule, winning_key, the argument checks -- with the bits they have here, so it includes this file with
-// RF_MESH_RASTER_DEVICE_ONLY defined: the kernels and the entry points below are then left out, everything else is the same text.
-#include "rf_device.h"
+// texel_taps of mesh_raster.h are the two device functions both kernels call, so a tap record holds the bits the shade kernel
+// fetches through.  thr3ed_atom_amd/texture_fit.py turns the records of many views into the sparse matrix whose adjoint
+// csrc/texture_fit_kernels.hip sums.
+#include "mesh_raster.h"
 
 namespace {
 
-constexpr int kRasterBlock = 256;
-constexpr int kMaxImageEdge = 16384;
-constexpr int kLaneBox = 8;  // boxes of at most kLaneBox x kLaneBox pixels stay on their lane; the wave path walks blocks of this edge
-constexpr unsigned long long kNoHit = ~0ull;
-
-struct RasterCamera {
-  int H, W;
-  float focal;
-  float R[9], t[3];
-};
-
-struct RasterArgs {
-  RasterCamera cam;
-  const float* vertices;
-  const long long* faces;
-  long long num_vertices, num_faces;
-  float near;
-  int cull;
-};
-
-// one face as a ray sees it: c[k] = the cross product of edge k's corners taken from the lower to the higher vertex index, flip[k]
-// whether the face runs along that edge the other way; zk[k] the camera depths
-struct RasterFace {
-  float c[3][3];
-  bool flip[3];
-  float zk[3];
-};
-
-__device__ __forceinline__ void cross3(const float* a, const float* b, float* out) {
-  out[0] = a[1] * b[2] - a[2] * b[1];
-  out[1] = a[2] * b[0] - a[0] * b[2];
-  out[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// vi: the three vertex indices (checked by the caller), v: their positions
-__device__ __forceinline__ RasterFace raster_face(const RasterCamera& cam, const unsigned long long (&vi)[3], const float (&v)[3][3]) {
-  RasterFace f;
-  float p[3][3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int x = 0; x < 3; ++x) p[k][x] = v[k][x] - cam.t[x];
-    f.zk[k] = -((p[k][0] * cam.R[2] + p[k][1] * cam.R[5]) + p[k][2] * cam.R[8]);
-  }
-  // edge k runs from corner (k + 1) % 3 to corner (k + 2) % 3; evaluated from the lower to the higher vertex index (see the top)
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int a = (k + 1) % 3, b = (k + 2) % 3;
-    f.flip[k] = vi[a] > vi[b];
-    if (f.flip[k])
-      cross3(p[b], p[a], f.c[k]);
-    else
-      cross3(p[a], p[b], f.c[k]);
-  }
-  return f;
-}
-
-struct RasterHit {
-  bool hit;
-  float w[3], z;
-};
-
-// the edge values e_k of pixel (i, j) on one face and their sum s = (e0 + e1) + e2: the ONLY place they are computed
-__device__ __forceinline__ float raster_edges(const RasterCamera& cam, const RasterFace& f, int i, int j, float (&e)[3]) {
-  float d[3];
-  pixel_ray(i, j, cam.H, cam.W, cam.focal, cam.R, d);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float t = (f.c[k][0] * d[0] + f.c[k][1] * d[1]) + f.c[k][2] * d[2];
-    e[k] = f.flip[k] ? -t : t;
-  }
-  return (e[0] + e[1]) + e[2];
-}
-
-// the coverage rule, the barycentrics and the depth of pixel (i, j) on one face: the ONLY place they are computed
-__device__ __forceinline__ RasterHit raster_hit(const RasterCamera& cam, const RasterFace& f, int i, int j, int cull) {
-  float e[3];
-  const float s = raster_edges(cam, f, i, j, e);
-  const bool neg = e[0] <= 0.0f && e[1] <= 0.0f && e[2] <= 0.0f, pos = e[0] >= 0.0f && e[1] >= 0.0f && e[2] >= 0.0f;
-  RasterHit h;
-  h.hit = (neg || (pos && !cull)) && s != 0.0f;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) h.w[k] = e[k] / s;
-  h.z = f.zk[0] + (h.w[1] * (f.zk[1] - f.zk[0]) + h.w[2] * (f.zk[2] - f.zk[0]));
-  h.hit = h.hit && h.z >= 0.0f && h.z <= 3.0e38f;  // (a depth whose bits would not order like the number is no hit; NaN fails both)
-  return h;
-}
-
-// loads face t: false (and the status word set) when it indexes outside the vertices
-__device__ __forceinline__ bool load_face(const RasterArgs& a, long long t, unsigned long long (&vi)[3], float (&v)[3][3], int* status) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) vi[c] = (unsigned long long)a.faces[3 * t + c];
-  const unsigned long long V = (unsigned long long)a.num_vertices;
-  if (vi[0] >= V || vi[1] >= V || vi[2] >= V) {
-    if (status) *status = 1;  // (a plain store of one value: whichever lane wins, the word reads 1)
-    return false;
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int x = 0; x < 3; ++x) v[c][x] = a.vertices[3 * vi[c] + x];
-  return true;
-}
-
-#ifndef RF_MESH_RASTER_DEVICE_ONLY
 // The conservative pixel box [j0, j1] x [i0, i1] of a face whose corners all have z_k >= near >= 0: the projected corners, widened by
 // a bound on the float32 error of the projection plus one pixel, clipped to the image.  A corner whose depth is not safely positive
 // (or anything not finite) gives the whole image: conservative is all the box has to be, the coverage rule decides.
@@ -255,8 +131,6 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_visibility_kernel(Ra
   }
 }
 
-#endif  // RF_MESH_RASTER_DEVICE_ONLY
-
 struct ShadeArgs {
   const unsigned long long* vis;
   const float* uvs;      // [T, 3, 2] or nullptr
@@ -270,37 +144,6 @@ struct ShadeArgs {
   float* bary;  // or nullptr
 };
 
-// the face index t a visibility key names: false when nothing was hit or the key names no face of this mesh (the shade pass then gives
-// the face id -1); csrc/mesh_fit_kernels.hip decodes its keys with this function too
-__device__ __forceinline__ bool winning_key(const RasterArgs& a, unsigned long long key, long long& t) {
-  t = (long long)(key & 0xffffffffull);
-  return !(key == kNoHit || t >= a.num_faces);
-}
-
-// the winning face of a pixel as the visibility buffer recorded it (defined below the shade kernel)
-__device__ __forceinline__ bool winning_hit(const RasterArgs& a, unsigned long long key, int i, int j, long long& t, unsigned long long (&vi)[3], RasterHit& h);
-
-// the four taps of the bilinear fetch at the interpolated UVs of a hit: the ONLY place they are computed (the shade kernel fetches
-// through them, the taps kernel records them)
-struct TexelTaps {
-  int x0, x1, y0, y1;
-  float fx, fy;
-};
-
-__device__ __forceinline__ TexelTaps texel_taps(const float* uv, const float (&w)[3], int Ht, int Wt) {
-  const float u = (w[0] * uv[0] + w[1] * uv[2]) + w[2] * uv[4];
-  const float vv = (w[0] * uv[1] + w[1] * uv[3]) + w[2] * uv[5];
-  const float x = u * (float)Wt - 0.5f, y = (1.0f - vv) * (float)Ht - 0.5f;
-  const float xf = floorf(x), yf = floorf(y);
-  TexelTaps p;
-  p.fx = x - xf, p.fy = y - yf;
-  // (clamped as floats first, so that the conversion is defined for every value; NaN goes to 0)
-  p.x0 = (int)fminf(fmaxf(xf, 0.0f), (float)(Wt - 1)), p.x1 = (int)fminf(fmaxf(xf + 1.0f, 0.0f), (float)(Wt - 1));
-  p.y0 = (int)fminf(fmaxf(yf, 0.0f), (float)(Ht - 1)), p.y1 = (int)fminf(fmaxf(yf + 1.0f, 0.0f), (float)(Ht - 1));
-  return p;
-}
-
-#ifndef RF_MESH_RASTER_DEVICE_ONLY
 __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterArgs a, ShadeArgs s) {
   const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
   if (pix >= (long long)a.cam.H * a.cam.W) return;
@@ -315,15 +158,11 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterA
 #pragma unroll
     for (int k = 0; k < 3; ++k) w[k] = h.w[k];
     if (s.colour && s.texture) {
-      const TexelTaps p = texel_taps(s.uvs + 6 * t, w, s.Ht, s.Wt);
+      const BilinearTaps p = texel_taps(s.uvs + 6 * t, w, s.Ht, s.Wt);
       const float* r0 = s.texture + 3ll * ((long long)p.y0 * s.Wt);
       const float* r1 = s.texture + 3ll * ((long long)p.y1 * s.Wt);
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float top = (1.0f - p.fx) * r0[3 * p.x0 + ch] + p.fx * r0[3 * p.x1 + ch];
-        const float bot = (1.0f - p.fx) * r1[3 * p.x0 + ch] + p.fx * r1[3 * p.x1 + ch];
-        rgb[ch] = (1.0f - p.fy) * top + p.fy * bot;
-      }
+      for (int ch = 0; ch < 3; ++ch) rgb[ch] = bilinear_blend(p, r0[3 * p.x0 + ch], r0[3 * p.x1 + ch], r1[3 * p.x0 + ch], r1[3 * p.x1 + ch]);
     } else if (s.colour && s.colours) {
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch)
@@ -342,19 +181,6 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_shade_kernel(RasterA
   }
 }
 
-#endif  // RF_MESH_RASTER_DEVICE_ONLY
-
-// the winning face of a pixel as the visibility buffer recorded it: false when nothing was hit (or the key names no face of this
-// mesh); else t, vi and the hit re-evaluated with the device functions of the visibility pass (the same bits)
-__device__ __forceinline__ bool winning_hit(const RasterArgs& a, unsigned long long key, int i, int j, long long& t, unsigned long long (&vi)[3], RasterHit& h) {
-  if (!winning_key(a, key, t)) return false;
-  float v[3][3];
-  if (!load_face(a, t, vi, v, nullptr)) return false;
-  h = raster_hit(a.cam, raster_face(a.cam, vi, v), i, j, a.cull);
-  return true;
-}
-
-#ifndef RF_MESH_RASTER_DEVICE_ONLY
 // one record per pixel: what the shade kernel computes before its fetch (x0 = 0xffff: no hit; texture edges are at most 16384)
 __global__ __launch_bounds__(kRasterBlock) void mesh_raster_taps_kernel(RasterArgs a, const unsigned long long* vis, const float* uvs, int Ht, int Wt, RFTextureTap* taps) {
   const long long pix = (long long)blockIdx.x * kRasterBlock + threadIdx.x;
@@ -367,43 +193,15 @@ __global__ __launch_bounds__(kRasterBlock) void mesh_raster_taps_kernel(RasterAr
   unsigned long long vi[3];
   RasterHit h;
   if (winning_hit(a, vis[pix], i, j, t, vi, h)) {
-    const TexelTaps p = texel_taps(uvs + 6 * t, h.w, Ht, Wt);
+    const BilinearTaps p = texel_taps(uvs + 6 * t, h.w, Ht, Wt);
     rec.x0 = (uint16_t)p.x0, rec.x1 = (uint16_t)p.x1, rec.y0 = (uint16_t)p.y0, rec.y1 = (uint16_t)p.y1;
     rec.fx = p.fx, rec.fy = p.fy;
   }
   taps[pix] = rec;
 }
 
-#endif  // RF_MESH_RASTER_DEVICE_ONLY
-
-// the checks both entry points share, after their pointer checks: RF_ERR_BAD_SHAPE, then RF_ERR_UNSUPPORTED
-int check_raster(const RFCamera* cam, int64_t num_vertices, int64_t num_faces, float near, uint32_t flags) {
-  if (num_vertices < 0 || num_faces < 0 || num_faces >= (1ll << 31)) return RF_ERR_BAD_SHAPE;
-  if (cam->height < 1 || cam->height > kMaxImageEdge || cam->width < 1 || cam->width > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
-  if (!std::isfinite(cam->focal) || !(cam->focal > 0.0f)) return RF_ERR_BAD_SHAPE;
-  for (int k = 0; k < 12; ++k)
-    if (!std::isfinite(cam->pose[k])) return RF_ERR_BAD_SHAPE;
-  if (!std::isfinite(near) || !(near >= 0.0f)) return RF_ERR_BAD_SHAPE;
-  if (flags & ~(uint32_t)(RF_FLAG_WHITE_BKGD | RF_RASTER_CULL_BACKFACES)) return RF_ERR_UNSUPPORTED;
-  return RF_OK;
-}
-
-RasterArgs raster_args(const RFCamera* cam, const float* vertices, int64_t num_vertices, const int64_t* faces, int64_t num_faces, float near, uint32_t flags) {
-  RasterArgs a;
-  a.cam.H = cam->height, a.cam.W = cam->width, a.cam.focal = cam->focal;
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) a.cam.R[3 * r + c] = cam->pose[4 * r + c];
-    a.cam.t[r] = cam->pose[4 * r + 3];
-  }
-  a.vertices = vertices, a.faces = (const long long*)faces;
-  a.num_vertices = num_vertices, a.num_faces = num_faces;
-  a.near = near, a.cull = (flags & RF_RASTER_CULL_BACKFACES) ? 1 : 0;
-  return a;
-}
-
 }  // namespace
 
-#ifndef RF_MESH_RASTER_DEVICE_ONLY
 extern "C" {
 
 int rf_mesh_raster_visibility(const RFCamera* camera, const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
@@ -429,7 +227,7 @@ int rf_mesh_raster_shade(const RFCamera* camera, const float* vertices_dev, int6
   if (colour_dev && !texture_dev && !colours_dev) return RF_ERR_NULL_POINTER;        // a colour image needs a source
   const int rc = check_raster(camera, num_vertices, num_faces, 0.0f, 0u);
   if (rc != RF_OK) return rc;
-  if (texture_dev && (texture_height < 1 || texture_height > kMaxImageEdge || texture_width < 1 || texture_width > kMaxImageEdge)) return RF_ERR_BAD_SHAPE;
+  if (texture_dev && !image_shape_ok(texture_height, texture_width)) return RF_ERR_BAD_SHAPE;
   if (flags & ~(uint32_t)(RF_FLAG_WHITE_BKGD | RF_RASTER_CULL_BACKFACES)) return RF_ERR_UNSUPPORTED;
   const RasterArgs a = raster_args(camera, vertices_dev, num_vertices, faces_dev, num_faces, 0.0f, flags);
   ShadeArgs s;
@@ -450,7 +248,7 @@ int rf_mesh_raster_taps(const RFCamera* camera, const float* vertices_dev, int64
   if ((num_vertices > 0 && !vertices_dev) || (num_faces > 0 && (!faces_dev || !uvs_dev))) return RF_ERR_NULL_POINTER;
   const int rc = check_raster(camera, num_vertices, num_faces, 0.0f, 0u);
   if (rc != RF_OK) return rc;
-  if (texture_height < 1 || texture_height > kMaxImageEdge || texture_width < 1 || texture_width > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
+  if (!image_shape_ok(texture_height, texture_width)) return RF_ERR_BAD_SHAPE;
   if (flags & ~(uint32_t)(RF_FLAG_WHITE_BKGD | RF_RASTER_CULL_BACKFACES)) return RF_ERR_UNSUPPORTED;
   const RasterArgs a = raster_args(camera, vertices_dev, num_vertices, faces_dev, num_faces, 0.0f, flags);
   const long long total = (long long)camera->height * camera->width;  // <= 2^28
@@ -460,4 +258,3 @@ int rf_mesh_raster_taps(const RFCamera* camera, const float* vertices_dev, int64
 }
 
 }  // extern "C"
-#endif  // RF_MESH_RASTER_DEVICE_ONLY

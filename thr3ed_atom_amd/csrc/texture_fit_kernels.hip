@@ -3,21 +3,18 @@
 // and the measurements, docs/texture_fit_errors.md the error bound, tests/texture_fit_model.py the float64 model.
 //
 // Forward.  One lane per pixel over the tap records of all views (rf_mesh_raster_taps of mesh_raster_kernels.hip): the fetch of the
-// shade kernel, its operations in its order (top, bot, then the fy blend; the library is built with -ffp-contract=off), so the colour
-// is render_mesh's bit for bit.  Nothing is rasterised again.
+// shade kernel through the same bilinear_blend of view_camera.h (top, bot, then the fy blend; the library is built with
+// -ffp-contract=off), so the colour is render_mesh's bit for bit.  Nothing is rasterised again.
 //
-// Backward.  The transposed map in gather form: one segment of (pixel, weight) entries per texel, built once per sampler.  One lane
-// per texel sums a short segment in entry order.  A segment longer than the threshold -- a face of a coarse patch that fills the
-// frame of many views puts 10^5 entries on one texel -- would leave 63 lanes waiting for one, so it is handed to the whole wavefront
-// by ballot, as the visibility kernel hands over its large boxes: lane l sums entries l, l + 64, ... in entry order, and a fixed
-// shuffle tree combines the 64 partial sums.  No atomics, no LDS, no barrier; the additions and their order are a function of the entry
-// list and the threshold alone.  Every texel is written, 0 for an empty segment.
-#include "rf_device.h"
+// Backward.  The transposed map in gather form: one segment of (pixel, weight) entries per texel, built once per sampler, summed by
+// segment_sum of segment_sum.h.  A segment longer than the threshold -- a face of a coarse patch that fills the frame of many views
+// puts 10^5 entries on one texel -- goes to the whole wavefront, as the visibility kernel hands over its large boxes.
+#include "segment_sum.h"
+#include "view_camera.h"
 
 namespace {
 
 constexpr int kFitBlock = 256;
-constexpr int kMaxImageEdge = 16384;
 constexpr int kLongSegment = 16;  // segments of more entries go to the wavefront (DESIGN.md section 24 has the A/B that chose it)
 constexpr unsigned int kNoTap = 0xffffu;
 
@@ -35,11 +32,7 @@ __global__ __launch_bounds__(kFitBlock) void texture_sample_kernel(const RFTextu
       const float* r1 = texture + 3ll * ((long long)p.y1 * Wt);
       const int x0 = p.x0, x1 = p.x1;
 #pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float top = (1.0f - p.fx) * r0[3 * x0 + ch] + p.fx * r0[3 * x1 + ch];
-        const float bot = (1.0f - p.fx) * r1[3 * x0 + ch] + p.fx * r1[3 * x1 + ch];
-        rgb[ch] = (1.0f - p.fy) * top + p.fy * bot;
-      }
+      for (int ch = 0; ch < 3; ++ch) rgb[ch] = bilinear_blend(p, r0[3 * x0 + ch], r0[3 * x1 + ch], r1[3 * x0 + ch], r1[3 * x1 + ch]);
     }
   }
 #pragma unroll
@@ -57,45 +50,20 @@ __device__ __forceinline__ void add_entry(const RFTextureTapEntry& e, const floa
   for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + e.weight * g[ch];
 }
 
+// what segment_sum adds for entry e of the list
+struct AddTapEntry {
+  const RFTextureTapEntry* entries;
+  const float* grad_colour;
+  long long P;
+  int* status;
+  __device__ __forceinline__ void operator()(long long e, float (&acc)[3]) const { add_entry(entries[e], grad_colour, P, acc, status); }
+};
+
 __global__ __launch_bounds__(kFitBlock) void texture_sample_backward_kernel(const float* __restrict__ grad_colour, long long P, const long long* __restrict__ offsets,
                                                                             const RFTextureTapEntry* __restrict__ entries, long long E, long long texels,
                                                                             int long_segment, float* __restrict__ grad_texture, int* status) {
-  const long long k = (long long)blockIdx.x * kFitBlock + threadIdx.x;
-  const int lane = (int)(threadIdx.x & 63);
-  // (no lane returns early: the ballot loop below needs the whole wavefront)
-  long long lo = 0, hi = 0;
-  if (k < texels) {  // (clamped: a malformed offset list reads no entry outside [0, E))
-    lo = min(max(offsets[k], 0ll), E);
-    hi = min(max(offsets[k + 1], lo), E);
-  }
-  const bool is_long = hi - lo > (long long)long_segment;
-  if (k < texels && !is_long) {
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    for (long long e = lo; e < hi; ++e) add_entry(entries[e], grad_colour, P, acc, status);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) grad_texture[3 * k + ch] = acc[ch];
-  }
-  unsigned long long todo = __ballot(is_long);
-  while (todo) {  // (wave-uniform)
-    const int src = __ffsll((long long)todo) - 1;
-    todo &= todo - 1;
-    const long long slo = __shfl(lo, src, 64), shi = __shfl(hi, src, 64);
-    float acc[3] = {0.0f, 0.0f, 0.0f};
-    for (long long e = slo + lane; e < shi; e += 64) add_entry(entries[e], grad_colour, P, acc, status);
-#pragma unroll
-    for (int step = 32; step >= 1; step >>= 1) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + __shfl_down(acc[ch], step, 64);  // (lanes past 63 - step read their own value: only lane 0 is used)
-    }
-    if (lane == 0) {
-      const long long dst = k + src;  // (lane 0's texel is the first of the wavefront's 64)
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) grad_texture[3 * dst + ch] = acc[ch];
-    }
-  }
+  segment_sum<3, kFitBlock>(offsets, E, texels, long_segment, grad_texture, AddTapEntry{entries, grad_colour, P, status});
 }
-
-bool texture_shape_ok(int32_t height, int32_t width) { return height >= 1 && height <= kMaxImageEdge && width >= 1 && width <= kMaxImageEdge; }
 
 }  // namespace
 
@@ -105,7 +73,7 @@ int rf_texture_sample(const void* taps_dev, int64_t num_pixels, const float* tex
                       float background, uint32_t flags, float* colour_dev, int32_t* status_dev, void* stream) {
   if (!texture_dev || !status_dev) return RF_ERR_NULL_POINTER;
   if (num_pixels > 0 && (!taps_dev || !colour_dev)) return RF_ERR_NULL_POINTER;
-  if (num_pixels < 0 || num_pixels >= (1ll << 31) || !texture_shape_ok(texture_height, texture_width)) return RF_ERR_BAD_SHAPE;
+  if (num_pixels < 0 || num_pixels >= (1ll << 31) || !image_shape_ok(texture_height, texture_width)) return RF_ERR_BAD_SHAPE;
   if (!std::isfinite(background) || !(background >= 0.0f)) return RF_ERR_BAD_SHAPE;
   if (flags) return RF_ERR_UNSUPPORTED;
   if (num_pixels == 0) return RF_OK;
@@ -120,7 +88,7 @@ int rf_texture_sample_backward(const float* grad_colour_dev, int64_t num_pixels,
                                float* grad_texture_dev, int32_t* status_dev, void* stream) {
   if (!offsets_dev || !grad_texture_dev || !status_dev) return RF_ERR_NULL_POINTER;
   if ((num_pixels > 0 && !grad_colour_dev) || (num_entries > 0 && !entries_dev)) return RF_ERR_NULL_POINTER;
-  if (num_pixels < 0 || num_pixels >= (1ll << 31) || !texture_shape_ok(texture_height, texture_width)) return RF_ERR_BAD_SHAPE;
+  if (num_pixels < 0 || num_pixels >= (1ll << 31) || !image_shape_ok(texture_height, texture_width)) return RF_ERR_BAD_SHAPE;
   if (num_entries < 0 || num_entries >= (1ll << 33) || long_segment < 0) return RF_ERR_BAD_SHAPE;
   if (flags) return RF_ERR_UNSUPPORTED;
   const long long texels = (long long)texture_height * texture_width;  // <= 2^28

@@ -23,15 +23,14 @@
 // that query_offset's channel arithmetic folds at compile time, and under DIFFUSE only the k = 0 channels are addressed (the base
 // record in split / bricked storage).  A face index outside [0, V) stores 1 to the status word and bakes zeros; it is never used
 // as an address.
-#include "rf_device.h"
 #include "texture_atlas.h"
+#include "view_camera.h"
 
 namespace {
 
 constexpr int kBakeBlock = 256;
 constexpr int kMinPatch = 2, kMaxPatch = 64;
 constexpr int kMaxSamples = 256;
-constexpr int kMaxImageEdge = 16384;
 
 struct BakeArgs {
   const float* vertices;

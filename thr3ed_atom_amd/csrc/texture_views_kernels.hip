@@ -11,7 +11,8 @@
 //   C = the bilinear fetch of image k at (x - 1/2, y - 1/2), taps clamped; m = the same fetch of the alpha plane, or 1
 //   accum.rgb += omega m (C - (1 - m) background), accum.w += omega m m, count += 1
 // -- the inverse of pixel_ray of rf_device.h (pixel (i, j) has its centre at (j + 1/2, i + 1/2)), a shadow-map test with a bias
-// against the depth rf_mesh_raster_visibility wrote, and the least-squares texel of pixels read as C = m c + (1 - m) background.
+// against the depth rf_mesh_raster_visibility wrote, the bilinear fetch of view_camera.h, and the least-squares texel of pixels read as
+// C = m c + (1 - m) background.
 //
 // The kernel.  ONE launch per chunk of at most 16 views, one lane per texel, block-major like the bake (a wave covers at most four
 // faces, so its texels project next to each other and its taps share lines).  The cameras travel BY VALUE in the kernel's argument
@@ -20,17 +21,14 @@
 // loads its accumulator, adds its views in order and stores it -- no atomics, two calls give the same bits, and successive calls over
 // chunks of views do the float additions of one long loop.  Unowned texels are not touched.  A face index outside [0, V) stores 1 to
 // the status word and leaves its texels as they were; it is never used as an address.
-#include "rf_device.h"
 #include "texture_atlas.h"
+#include "view_camera.h"
 
 namespace {
 
 constexpr int kViewsBlock = 256;
-constexpr int kMaxViews = 16;
 constexpr int kMinPatch = 2, kMaxPatch = 64;
-constexpr int kMaxImageEdge = 16384;
 constexpr int kMaxCosPower = 8;
-constexpr unsigned long long kNoHit = ~0ull;
 
 struct ViewsArgs {
   const float* vertices;
@@ -48,28 +46,6 @@ struct ViewsArgs {
   int* status;
   RFCamera cams[kMaxViews];  // (height and width are H and W in every one)
 };
-
-// the four taps and the two weights of a bilinear fetch at (x, y) of an H x W image, taps clamped to the image
-struct ViewTaps {
-  int x0, x1, y0, y1;
-  float fx, fy;
-};
-
-__device__ __forceinline__ ViewTaps view_taps(float x, float y, int H, int W) {
-  ViewTaps s;
-  const float xf = floorf(x), yf = floorf(y);
-  s.fx = x - xf, s.fy = y - yf;
-  // (clamped as floats first, so that the conversion is defined for every value)
-  s.x0 = (int)fminf(fmaxf(xf, 0.0f), (float)(W - 1)), s.x1 = (int)fminf(fmaxf(xf + 1.0f, 0.0f), (float)(W - 1));
-  s.y0 = (int)fminf(fmaxf(yf, 0.0f), (float)(H - 1)), s.y1 = (int)fminf(fmaxf(yf + 1.0f, 0.0f), (float)(H - 1));
-  return s;
-}
-
-__device__ __forceinline__ float view_blend(const ViewTaps& s, float a00, float a01, float a10, float a11) {
-  const float top = (1.0f - s.fx) * a00 + s.fx * a01;
-  const float bot = (1.0f - s.fx) * a10 + s.fx * a11;
-  return (1.0f - s.fy) * top + s.fy * bot;
-}
 
 __global__ __launch_bounds__(kViewsBlock) void texture_project_views_kernel(ViewsArgs a) {
   const int B = a.block, P = a.patch;
@@ -113,15 +89,15 @@ __global__ __launch_bounds__(kViewsBlock) void texture_project_views_kernel(View
     if (!(z <= zbuf + a.depth_bias)) continue;
     float omega = 1.0f;
     for (int q = 0; q < a.cos_power; ++q) omega = omega * cs;
-    const ViewTaps s = view_taps(x - 0.5f, y - 0.5f, H, W);
+    const BilinearTaps s = bilinear_taps(x - 0.5f, y - 0.5f, H, W);
     const long long r0 = view + (long long)s.y0 * W, r1 = view + (long long)s.y1 * W;
     const long long o00 = r0 + s.x0, o01 = r0 + s.x1, o10 = r1 + s.x0, o11 = r1 + s.x1;
-    const float m = a.alphas ? view_blend(s, a.alphas[o00], a.alphas[o01], a.alphas[o10], a.alphas[o11]) : 1.0f;
+    const float m = a.alphas ? bilinear_blend(s, a.alphas[o00], a.alphas[o01], a.alphas[o10], a.alphas[o11]) : 1.0f;
     const float wm = omega * m;
     const float rest = (1.0f - m) * a.background;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-      const float c = view_blend(s, a.images[3 * o00 + ch], a.images[3 * o01 + ch], a.images[3 * o10 + ch], a.images[3 * o11 + ch]);
+      const float c = bilinear_blend(s, a.images[3 * o00 + ch], a.images[3 * o01 + ch], a.images[3 * o10 + ch], a.images[3 * o11 + ch]);
       acc[ch] = acc[ch] + wm * (c - rest);
     }
     acc[3] = acc[3] + wm * m;
@@ -150,14 +126,7 @@ int rf_texture_project_views(const float* vertices_dev, int64_t num_vertices, co
   const int block = patch + 4;
   if ((long long)cols * block > kMaxImageEdge || (long long)rows * block > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
   if (2ll * cols * rows < num_faces) return RF_ERR_BAD_SHAPE;
-  for (int k = 0; k < num_views; ++k) {
-    const RFCamera& cam = cameras[k];
-    if (cam.height < 1 || cam.height > kMaxImageEdge || cam.width < 1 || cam.width > kMaxImageEdge) return RF_ERR_BAD_SHAPE;
-    if (cam.height != cameras[0].height || cam.width != cameras[0].width) return RF_ERR_BAD_SHAPE;
-    if (!std::isfinite(cam.focal) || !(cam.focal > 0.0f)) return RF_ERR_BAD_SHAPE;
-    for (int e = 0; e < 12; ++e)
-      if (!std::isfinite(cam.pose[e])) return RF_ERR_BAD_SHAPE;
-  }
+  if (!view_cameras_ok(cameras, num_views)) return RF_ERR_BAD_SHAPE;
   if (!std::isfinite(near) || !(near >= 0.0f) || !std::isfinite(depth_bias) || !(depth_bias >= 0.0f)) return RF_ERR_BAD_SHAPE;
   if (!std::isfinite(background) || !(background >= 0.0f)) return RF_ERR_BAD_SHAPE;
   if (!(min_cos >= 0.0f) || !(min_cos < 1.0f)) return RF_ERR_BAD_SHAPE;
@@ -173,7 +142,7 @@ int rf_texture_project_views(const float* vertices_dev, int64_t num_vertices, co
   a.near = near, a.depth_bias = depth_bias, a.min_cos = min_cos, a.background = background;
   a.cos_power = cos_power, a.two_sided = (flags & RF_TEXTURE_VIEWS_TWO_SIDED) ? 1 : 0;
   a.accum = accum_dev, a.count = count_dev, a.status = status_dev;
-  for (int k = 0; k < kMaxViews; ++k) a.cams[k] = cameras[k < num_views ? k : 0];  // (the tail is never read; it is not left uninitialised)
+  fill_view_cameras(a.cams, cameras, num_views);
   const long long total = (long long)cols * block * rows * block;  // <= 2^28
   hipLaunchKernelGGL(texture_project_views_kernel, dim3((unsigned)((total + kViewsBlock - 1) / kViewsBlock)), dim3(kViewsBlock), 0, (hipStream_t)stream, a);
   return launch_status();

@@ -15,7 +15,6 @@ import ctypes as C
 import math
 from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
-import numpy as np
 import torch
 from torch import Tensor
 
@@ -73,10 +72,8 @@ class MeshGeometryRenderer:
         self.near = _marshal.non_negative(near, "near")
         self.flags = _lib.RASTER_CULL_BACKFACES if cull_backfaces else 0
         self.long_segment = 0  # (the library's default; tools/mesh_fit_time.py and the tests set others)
-        from .texture_fit import _identity_pose
-
         self.cams = [_marshal.checked_camera(pose, camera_intrinsics) for pose in poses]
-        _marshal.checked_camera(_identity_pose(), camera_intrinsics)  # (the intrinsics' own errors, even with zero views)
+        _marshal.checked_camera(_marshal.identity_pose(), camera_intrinsics)  # (the intrinsics' own errors, even with zero views)
         self.N, self.H, self.W = len(self.cams), int(camera_intrinsics[0]), int(camera_intrinsics[1])
         self.P = self.N * self.H * self.W
         if self.P >= MAX_PIXELS:
@@ -104,10 +101,7 @@ class MeshGeometryRenderer:
             stream = _marshal.stream(dev)
             visibility = torch.empty((H, W), dtype=torch.int64, device=dev)
             for k, cam in enumerate(self.cams):
-                visibility.fill_(-1)  # all ones: nothing hit
-                rc = lib.rf_mesh_raster_visibility(C.byref(cam), vertices.data_ptr(), V, self.faces.data_ptr(), T, self.near, self.flags, visibility.data_ptr(),
-                                                   self.status.data_ptr(), stream)
-                _lib.check(rc, "rf_mesh_raster_visibility")
+                _marshal.raster_visibility(cam, vertices, self.faces, self.near, self.flags, visibility, self.status)
                 rc = lib.rf_mesh_raster_coverage(C.byref(cam), vertices.data_ptr(), V, self.faces.data_ptr(), T, visibility.data_ptr(), self.flags, depth[k].data_ptr(),
                                                  coverage[k].data_ptr(), face_ids[k].data_ptr(), stream)
                 _lib.check(rc, "rf_mesh_raster_coverage")
@@ -119,10 +113,7 @@ class MeshGeometryRenderer:
         if self._corners is None or self._corners[2] != V:
             flat = self.faces.view(-1)
             _, order = torch.sort(flat, stable=True)
-            counts = torch.bincount(flat.clamp(0, max(V - 1, 0)), minlength=V) if V and self.T else torch.zeros(V, dtype=torch.int64, device=self.device)
-            offsets = torch.zeros(V + 1, dtype=torch.int64, device=self.device)
-            offsets[1:] = torch.cumsum(counts, 0)
-            self._corners = (order.to(torch.int32).contiguous(), offsets, V)
+            self._corners = (order.to(torch.int32).contiguous(), _marshal.segment_offsets(flat.clamp(0, max(V - 1, 0)), V), V)
         return self._corners[0], self._corners[1]
 
     def hit_lists(self, face_ids: Tensor):
@@ -130,10 +121,7 @@ class MeshGeometryRenderer:
         ids = face_ids.view(-1)
         pixel = torch.nonzero(ids >= 0).view(-1)
         face, order = torch.sort(ids[pixel].to(torch.int64), stable=True)
-        counts = torch.bincount(face, minlength=self.T) if self.T else torch.zeros(0, dtype=torch.int64, device=self.device)
-        offsets = torch.zeros(self.T + 1, dtype=torch.int64, device=self.device)
-        offsets[1:] = torch.cumsum(counts, 0)
-        return pixel[order].to(torch.int32).contiguous(), offsets
+        return pixel[order].to(torch.int32).contiguous(), _marshal.segment_offsets(face, self.T)
 
     def _records(self, vertices: Tensor, face_ids: Tensor, coverage: Tensor, grad_depth: Tensor, grad_coverage: Tensor) -> Tensor:
         """stage 1: [P, 9] float32, written at the hit pixels only"""
@@ -227,13 +215,6 @@ def vertex_normals(vertices: Tensor, faces: Tensor) -> Tensor:
     return torch.where(length > 0, total / length.clamp(min=1e-30), torch.zeros_like(total))
 
 
-def _positive(value, name: str) -> float:
-    value = float(value)
-    if not (math.isfinite(value) and value > 0.0):
-        raise ValueError(f"{name} must be positive and finite, got {value!r}")
-    return value
-
-
 def _weight(value, name: str) -> float:
     value = float(value)
     if not (math.isfinite(value) and value >= 0.0):
@@ -273,10 +254,9 @@ def fit_mesh_to_views(mesh: Mesh, depths, alphas, poses: Sequence, camera_intrin
     N = len(poses)
     if len(depths) != N or len(alphas) != N:
         raise ValueError(f"{len(depths)} depths, {len(alphas)} alphas, {N} poses: the counts must match")
-    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
-        raise ValueError(f"iterations must be a non-negative integer, got {iterations!r}")
-    lr = None if lr is None else _positive(lr, "lr")
-    max_move = None if max_move is None else _positive(max_move, "max_move")
+    iterations = _marshal.iteration_count(iterations)
+    lr = None if lr is None else _marshal.positive(lr, "lr")
+    max_move = None if max_move is None else _marshal.positive(max_move, "max_move")
     depth_weight, mask_weight, laplacian_weight = _weight(depth_weight, "depth_weight"), _weight(mask_weight, "mask_weight"), _weight(laplacian_weight, "laplacian_weight")
     H, W = int(camera_intrinsics[0]), int(camera_intrinsics[1])
     dev, V = vertices.device, int(vertices.shape[0])
@@ -290,7 +270,7 @@ def fit_mesh_to_views(mesh: Mesh, depths, alphas, poses: Sequence, camera_intrin
             raise ValueError(f"the {name} of {N} views of {H} x {W} pixels must have shape {(N, H, W)}, got {tuple(given.shape)}")
         targets.append(given.detach().to(dev, torch.float32).contiguous())
     depths, alphas = targets
-    history = torch.zeros(int(iterations), dtype=torch.float32, device=dev)
+    history = torch.zeros(iterations, dtype=torch.float32, device=dev)
     moved = torch.zeros(V, dtype=torch.float32, device=dev)
     if not iterations or not V or not faces.shape[0] or not N:
         return MeshFit(mesh, history, moved)
@@ -306,7 +286,7 @@ def fit_mesh_to_views(mesh: Mesh, depths, alphas, poses: Sequence, camera_intrin
     param = start.clone().requires_grad_(True)
     optimiser = torch.optim.Adam([param], lr=lr)
     losses = []
-    for it in range(int(iterations)):
+    for it in range(iterations):
         optimiser.zero_grad(set_to_none=True)
         depth, coverage = renderer(param)
         value = fit_loss(depth, coverage, renderer.last_face_ids, depths, alphas, depth_weight, mask_weight)

@@ -95,10 +95,9 @@ def render_mesh(mesh: Mesh, camera_pose: CameraPose, camera_intrinsics: CameraIn
         _marshal.require_finite_vertices(vertices)
         flags = (_lib.FLAG_WHITE_BKGD if white_bkgd else 0) | (_lib.RASTER_CULL_BACKFACES if cull_backfaces else 0)
         stream = _marshal.stream(dev)
-        visibility = torch.full((H, W), -1, dtype=torch.int64, device=dev)  # all ones: nothing hit
+        visibility = torch.empty((H, W), dtype=torch.int64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        rc = lib.rf_mesh_raster_visibility(C.byref(cam), vertices.data_ptr(), V, faces.data_ptr(), T, near, flags, visibility.data_ptr(), status.data_ptr(), stream)
-        _lib.check(rc, "rf_mesh_raster_visibility")
+        _marshal.raster_visibility(cam, vertices, faces, near, flags, visibility, status)
         _marshal.require_faces_in_range(status, V)
         colour = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if has_colour else None
         depth = torch.empty((H, W, 1), dtype=torch.float32, device=dev)

@@ -206,11 +206,8 @@ class _ViewProjector:
             stream = _marshal.stream(self.dev)
             if self.visibility is None:
                 self.visibility = torch.empty((MAX_VIEWS, self.H, self.W), dtype=torch.int64, device=self.dev)
-            self.visibility[:n].fill_(-1)  # all ones: nothing hit
             for k in range(n):
-                rc = lib.rf_mesh_raster_visibility(C.byref(cams[k]), self.vertices.data_ptr(), self.V, self.faces.data_ptr(), self.T, self.near, 0,
-                                                   self.visibility[k].data_ptr(), self.status.data_ptr(), stream)
-                _lib.check(rc, "rf_mesh_raster_visibility")
+                _marshal.raster_visibility(cams[k], self.vertices, self.faces, self.near, 0, self.visibility[k], self.status)
             rc = lib.rf_texture_project_views(self.vertices.data_ptr(), self.V, self.faces.data_ptr(), self.T, self.layout.patch, self.layout.cols, self.layout.rows,
                                               n, cams, images.data_ptr(), self.visibility.data_ptr(), ptr(alphas), self.near,
                                               self.depth_bias, self.min_cos, self.cos_power, self.background, self.flags, self.accum.data_ptr(),

@@ -12,10 +12,8 @@ Only the texture gets a gradient.  Not done here: gradients to geometry, UVs, ca
 silhouettes), mini-batches of views, a conjugate-gradient solver for the L2 case, per-view exposure, seam blending, mip-mapped
 atlases."""
 import ctypes as C
-import math
 from typing import Callable, NamedTuple, Optional, Sequence
 
-import numpy as np
 import torch
 from torch import Tensor
 
@@ -71,7 +69,7 @@ class MeshTextureSampler:
         self.long_segment = 0  # (the library's default; tools/texture_fit_time.py sets others for its A/B)
         poses = list(poses)
         cams = [_marshal.checked_camera(pose, camera_intrinsics) for pose in poses]
-        _marshal.checked_camera(_identity_pose(), camera_intrinsics)  # (the intrinsics' own errors, even with zero views)
+        _marshal.checked_camera(_marshal.identity_pose(), camera_intrinsics)  # (the intrinsics' own errors, even with zero views)
         self.N, self.H, self.W = len(poses), int(camera_intrinsics[0]), int(camera_intrinsics[1])
         self.Ht, self.Wt = int(texture.shape[0]), int(texture.shape[1])
         self.P = self.N * self.H * self.W
@@ -91,10 +89,7 @@ class MeshTextureSampler:
                 visibility = torch.empty((self.H, self.W), dtype=torch.int64, device=dev)
                 per_view = self.taps.view(self.N, self.H * self.W, 4)
                 for k, cam in enumerate(cams):
-                    visibility.fill_(-1)  # all ones: nothing hit
-                    rc = lib.rf_mesh_raster_visibility(C.byref(cam), self.vertices.data_ptr(), V, self.faces.data_ptr(), T, self.near, flags, visibility.data_ptr(),
-                                                       self.status.data_ptr(), stream)
-                    _lib.check(rc, "rf_mesh_raster_visibility")
+                    _marshal.raster_visibility(cam, self.vertices, self.faces, self.near, flags, visibility, self.status)
                     rc = lib.rf_mesh_raster_taps(C.byref(cam), self.vertices.data_ptr(), V, self.faces.data_ptr(), T, visibility.data_ptr(), self.uvs.data_ptr(),
                                                  self.Ht, self.Wt, flags, per_view[k].data_ptr(), stream)
                     _lib.check(rc, "rf_mesh_raster_taps")
@@ -134,12 +129,6 @@ class MeshTextureSampler:
         return grad
 
 
-def _identity_pose():
-    from .camera import CameraPose
-
-    return CameraPose(torch.eye(3), torch.zeros(3, 1))
-
-
 def tap_fields(taps: Tensor):
     """RFTextureTap records as int32 words [P, 4] -> (x0, x1, y0, y1 int64 [P], fx, fy float32 [P])"""
     xs, ys = taps[:, 0].to(torch.int64), taps[:, 1].to(torch.int64)
@@ -151,7 +140,6 @@ def _transpose_taps(taps: Tensor, Wt: int, texels: int):
     """The transposed tap list of rf_texture_sample_backward: (offsets int64 [texels + 1], entries int32 [E, 2] = (pixel, weight bits),
     coverage int32 [texels]).  Every hit pixel gives four entries in the order (y0, x0), (y0, x1), (y1, x0), (y1, x1) with the weights
     (1 - fx)(1 - fy), fx (1 - fy), (1 - fx) fy, fx fy; a stable sort by texel keeps ties in ascending pixel order."""
-    dev = taps.device
     x0, x1, y0, y1, fx, fy = tap_fields(taps)
     pixel = torch.nonzero(x0 != NO_TAP).view(-1)
     x0, x1, y0, y1, fx, fy = (a[pixel] for a in (x0, x1, y0, y1, fx, fy))
@@ -160,17 +148,8 @@ def _transpose_taps(taps: Tensor, Wt: int, texels: int):
     weight = torch.stack([gx * gy, fx * gy, gx * fy, fx * fy], dim=1).view(-1)
     texel, order = torch.sort(texel, stable=True)
     entries = torch.stack([pixel.to(torch.int32).repeat_interleave(4)[order], weight[order].view(torch.int32)], dim=1).contiguous()
-    counts = torch.bincount(texel, minlength=texels) if texels else torch.zeros(0, dtype=torch.int64, device=dev)
-    offsets = torch.zeros(texels + 1, dtype=torch.int64, device=dev)
-    offsets[1:] = torch.cumsum(counts, 0)
-    return offsets, entries, counts.to(torch.int32)
-
-
-def _positive(value, name: str) -> float:
-    value = float(value)
-    if not (math.isfinite(value) and value > 0.0):
-        raise ValueError(f"{name} must be positive and finite, got {value!r}")
-    return value
+    offsets = _marshal.segment_offsets(texel, texels)
+    return offsets, entries, torch.diff(offsets).to(torch.int32)
 
 
 def fit_texture(mesh: Mesh, bake: TextureBake, images, poses: Sequence, camera_intrinsics, *, alphas=None, background: float = 0.0, iterations: int = 200,
@@ -192,9 +171,8 @@ def fit_texture(mesh: Mesh, bake: TextureBake, images, poses: Sequence, camera_i
     N = len(poses)
     if len(images) != N or (alphas is not None and len(alphas) != N):
         raise ValueError(f"{len(images)} images, {N} poses" + ("" if alphas is None else f", {len(alphas)} alphas") + ": the counts must match")
-    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 0:
-        raise ValueError(f"iterations must be a non-negative integer, got {iterations!r}")
-    lr = _positive(lr, "lr")
+    iterations = _marshal.iteration_count(iterations)
+    lr = _marshal.positive(lr, "lr")
     if loss not in ("l1", "l2"):
         raise ValueError(f"loss must be 'l1' or 'l2', got {loss!r}")
     dssim_weight = float(dssim_weight)
@@ -209,7 +187,7 @@ def fit_texture(mesh: Mesh, bake: TextureBake, images, poses: Sequence, camera_i
         if tuple(alphas.shape) != (N, H, W):
             raise ValueError(f"the alphas of {N} views of {H} x {W} pixels must have shape {(N, H, W)}, got {tuple(alphas.shape)}")
     dev = bake.texture.device if torch.is_tensor(bake.texture) else None
-    history = torch.zeros(int(iterations), dtype=torch.float32, device=dev)
+    history = torch.zeros(iterations, dtype=torch.float32, device=dev)
     sampler = MeshTextureSampler(mesh, bake, poses, camera_intrinsics, near=near, cull_backfaces=cull_backfaces, background=background)
     if not iterations or not sampler.num_entries:  # (no pixel taps any texel: every gradient is zero)
         return TextureFit(bake, history, sampler.coverage)
@@ -223,7 +201,7 @@ def fit_texture(mesh: Mesh, bake: TextureBake, images, poses: Sequence, camera_i
     texture = start.clone().requires_grad_(True)
     optimiser = torch.optim.Adam([texture], lr=lr)
     losses = []
-    for it in range(int(iterations)):
+    for it in range(iterations):
         optimiser.zero_grad(set_to_none=True)
         sampled = sampler(texture)
         pred = sampled if m is None else m * sampled + (1.0 - m) * sampler.background
