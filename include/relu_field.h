@@ -905,6 +905,40 @@ int rf_fuse_depth_views(const float* aabb_min, const float* aabb_max, const int3
                         const float* depths_dev, const float* alphas_dev, const float* images_dev, float near, float truncation, float min_alpha,
                         uint32_t flags, float* tsdf_sum_dev, int32_t* counts_dev, float* colour_sum_dev, void* stream);
 
+/* ---- Closest points on a triangle mesh (csrc/mesh_distance_kernels.hip; docs/mesh_distance_errors.md;
+ * thr3ed_atom_amd/mesh_distance.py builds the lists, samples surfaces and reduces the distances) -------------------------------------
+ * The search structure is a lattice of cells = (n_x, n_y, n_z) cubic cells (each in [1, 1024], n_x n_y n_z < 2^25) of edge h from
+ * `origin` (HOST arrays of 3).  The cell of a coordinate v along an axis is floor(fl32(fl32(v - origin) * r)), r = fl32(1 / h), clamped
+ * into [0, n - 1]; the key of a cell is (k_x n_y + k_y) n_z + k_z.  A face is registered in every cell of the cell range of its
+ * axis-aligned box.
+ * rf_mesh_grid_pairs: offsets_dev [num_faces + 1] int64 is the exclusive prefix sum of the cells per face (the caller computes it with
+ *   the rule above), num_pairs its last entry.  One lane per face writes keys_dev [num_pairs] int64 and pair_faces_dev [num_pairs]
+ *   int32 from offsets[f] on, x-major; a box of more than 64 cells is written by the whole wavefront.  A face that indexes outside the
+ *   vertices or has a non-finite corner writes nothing and sets status_dev[0] (int32, zeroed by the caller) to 1; one whose own count
+ *   differs from its offsets writes nothing and sets it to 2.  No atomics.
+ * rf_mesh_closest_points: cell_begin_dev [n_x n_y n_z + 1] int32 bounds every cell's segment of cell_faces_dev [num_pairs] int32 (the
+ *   pairs' faces stably sorted by key).  points_dev [num_points, 3] float32; order_dev [num_points] int64 or NULL is the order in which
+ *   lanes take the queries (a permutation; results land at the query's own index).  Per query: distance_dev [num_points] float32,
+ *   face_dev [num_points] int64, point_dev [num_points, 3] float32 = the smallest float32 distance over ALL faces under the rule of
+ *   docs/mesh_distance_errors.md (closest_on_face of csrc/mesh_distance.h), the lowest face index on an exact tie, and that face's
+ *   closest point; (+inf, -1, NaN) when no face lies within max_distance (inclusive; +inf: no limit).  The result does not depend on
+ *   the lattice, bit for bit.  rings_dev [num_points] int32 or NULL receives the Chebyshev radius at which the query stopped.
+ *   status_dev[0] is set to 1 for a non-finite query (which gets (+inf, -1, NaN)) or a face outside the vertices, to 2 for a list
+ *   entry outside its array.  One launch, no atomics, no LDS: one lane per query for the first two shells of cells, then the whole
+ *   wavefront per query that is still walking (the same minimum, the same bits).
+ * Before any launch, in this order: RF_ERR_NULL_POINTER (origin, cells, status_dev; every array a non-zero count needs),
+ * RF_ERR_BAD_SHAPE (a negative count, 2^31 or more vertices, faces or pairs, h or 1 / h not positive and finite, a non-finite origin, a
+ * cell count outside [1, 1024] or a lattice of 2^25 cells or more, a max_distance that is negative or NaN), RF_ERR_UNSUPPORTED (any
+ * flag bit: none is defined); then zero faces (or zero points) return RF_OK without a launch.  (Added to ABI version 4 compatibly: no
+ * existing struct or signature changed.) */
+int rf_mesh_grid_pairs(const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces, const float* origin, float h,
+                       const int32_t* cells, const int64_t* offsets_dev, int64_t num_pairs, int64_t* keys_dev, int32_t* pair_faces_dev, int32_t* status_dev,
+                       void* stream);
+int rf_mesh_closest_points(const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces, const float* origin, float h,
+                           const int32_t* cells, const int32_t* cell_begin_dev, const int32_t* cell_faces_dev, int64_t num_pairs, const float* points_dev,
+                           const int64_t* order_dev, int64_t num_points, float max_distance, uint32_t flags, float* distance_dev, int64_t* face_dev,
+                           float* point_dev, int32_t* rings_dev, int32_t* status_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

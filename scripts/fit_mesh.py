@@ -8,7 +8,8 @@ accumulated weight over a turn-table of views, through the anti-aliased coverage
 
 The views are those of scripts/render_mesh.py and scripts/bake_texture.py (--views N frames at --camera_pitch; the checkpoint's camera
 unless --view_height / --view_width / --view_focal say otherwise).  --max_move_voxels limits how far a vertex may go from where it
-started, in (smallest) voxel edges.  Bake textures AFTER the fit (scripts/bake_texture.py), so that they see the fitted surface.
+started, in (smallest) voxel edges; --distance_to_input prints how far the fitted surface lies from the input one (its Hausdorff distance
+is the guard against a too large limit).  Bake textures AFTER the fit (scripts/bake_texture.py), so that they see the fitted surface.
 """
 import os
 import sys
@@ -21,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import thr3ed_atom_amd as rf  # noqa: E402
 from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
+from thr3ed_atom_amd.mesh_distance import format_mesh_distance  # noqa: E402
 
 
 # fmt: off
@@ -40,6 +42,7 @@ from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
 @click.option("--view_width", type=click.IntRange(min=1), default=None, required=False, help="image width of the views (default: the checkpoint's camera)")
 @click.option("--view_focal", type=click.FLOAT, default=None, required=False, help="focal length of the views in pixels (default: the checkpoint's camera)")
 @click.option("--cull_backfaces", is_flag=True, default=False, help="draw only the faces whose outside looks at the camera")
+@click.option("--distance_to_input", is_flag=True, default=False, help="print the surface distance of the output against the input (Chamfer, Hausdorff lower bound; rf.mesh_distance)")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -68,6 +71,8 @@ def main(**kwargs) -> None:
     print(f"mesh fit: loss {ends} in {len(history)} iterations over {len(poses)} views of {intr[0]}x{intr[1]} (radius {radius:.6g}, pitch {config['camera_pitch']:.6g}); "
           f"V = {len(mesh.vertices)}, T = {len(mesh.faces)}; vertices moved {float(fit.moved.mean()) if len(mesh.vertices) else 0.0:.4g} on average, at most "
           f"{float(fit.moved.max()) if len(mesh.vertices) else 0.0:.4g} (limit {limit:.4g}) in {dt:.2f} s (incl. the field's renders) -> {config['output_path']}")
+    if config["distance_to_input"]:
+        print(format_mesh_distance(rf.mesh_distance(fit.mesh, mesh), "output", "input"))
 
 
 if __name__ == "__main__":

@@ -6,7 +6,8 @@ by vertex clustering with quadric-error representatives (thr3ed_atom_amd.mesh_si
     python scripts/simplify_mesh.py -i mesh.ply -o small.ply --target_faces 100000 --placement mean
 
 The PLY's uint8 colours are read as colour / 255 and its normals as they are: all-zero normals and all-255 colours -- what write_ply
-stores for a mesh without them -- pass through as data.  Opposed face pairs of collapsed thin sheets are kept; this is vertex
+stores for a mesh without them -- pass through as data.  --distance_to_input prints how far the result lies from the input (DESIGN.md
+section 27).  Opposed face pairs of collapsed thin sheets are kept; this is vertex
 clustering, not edge collapse.
 """
 import os
@@ -20,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import thr3ed_atom_amd as rf  # noqa: E402
 from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
+from thr3ed_atom_amd.mesh_distance import format_mesh_distance  # noqa: E402
 
 
 # fmt: off
@@ -30,6 +32,7 @@ from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
 @click.option("--target_faces", type=click.IntRange(min=0), default=None, required=False, help="the finest cells that leave at most this many faces")
 @click.option("--placement", type=click.Choice(["quadric", "mean"]), default="quadric", required=False, help="where a cluster's vertex goes")
 @click.option("--regularisation", type=click.FloatRange(min=1e-6, max=1.0), default=1e-3, required=False, help="pull of the quadric minimiser towards the cluster's mean vertex")
+@click.option("--distance_to_input", is_flag=True, default=False, help="print the surface distance of the output against the input (Chamfer, Hausdorff lower bound; rf.mesh_distance)")
 # fmt: on
 def main(**kwargs) -> None:
     config = dict(kwargs)
@@ -50,6 +53,8 @@ def main(**kwargs) -> None:
     print(f"{config['placement']}, cell size {stats.cell_size:.6g}: V = {len(mesh.vertices)} -> {len(out.vertices)}, T = {len(mesh.faces)} -> {len(out.faces)} "
           f"({stats.collapsed_faces} collapsed, {stats.merged_duplicates} duplicates merged, {stats.clusters} occupied cells) "
           f"in {1e3 * dt:.1f} ms (incl. host synchronisation) -> {config['output_path']}")
+    if config["distance_to_input"]:
+        print(format_mesh_distance(rf.mesh_distance(out, mesh), "output", "input"))
 
 
 if __name__ == "__main__":

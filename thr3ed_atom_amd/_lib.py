@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip", "mesh_distance_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -42,6 +42,7 @@ TEXTURE_VIEWS_MAX_VIEWS, TEXTURE_VIEWS_MAX_COS_POWER = 16, 8  # kMaxViews of csr
 TEXTURE_FIT_LONG_SEGMENT, TEXTURE_NO_TAP = 16, 0xFFFF  # kLongSegment, kNoTap of csrc/texture_fit_kernels.hip: longer segments of rf_texture_sample_backward go to the wavefront
 FUSE_CARVE = 128  # RF_FUSE_CARVE
 FUSE_MAX_VIEWS, FUSE_MAX_DIM = 16, 4096  # kMaxViews of csrc/view_camera.h, kMaxDim of csrc/fusion_kernels.hip: views per rf_fuse_depth_views call, nodes per axis
+MESH_DISTANCE_MAX_CELLS, MESH_DISTANCE_WIDE_FACE, MESH_DISTANCE_MAX_TABLE, MESH_DISTANCE_LANE_RINGS = 1024, 64, 1 << 25, 2  # kMaxGridCells, kWideFace, kMaxTable, kLaneRings of csrc/mesh_distance_kernels.hip: cells per axis, cells of a face box from which the wavefront writes its pairs, cells of a lattice, shells a lane walks before the wavefront takes its query
 MESH_FIT_LONG_SEGMENT = 16  # kLongSegment of csrc/mesh_fit_kernels.hip: longer segments of rf_mesh_geometry_backward_gather go to the wavefront
 SSIM_TILE = (16, 32)  # map rows x columns per workgroup of rf_ssim_forward (image rows x columns of rf_ssim_backward)
 STEP_FORWARD = 1
@@ -121,6 +122,8 @@ EXPORTED_SYMBOLS = [
     "rf_mesh_geometry_backward_pixels",
     "rf_mesh_geometry_backward_gather",
     "rf_fuse_depth_views",
+    "rf_mesh_grid_pairs",
+    "rf_mesh_closest_points",
 ]
 
 
@@ -415,6 +418,9 @@ def load() -> C.CDLL:
     lib.rf_mesh_geometry_backward_gather.argtypes = [vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, u32, vp, vp, vp, vp]
     # TSDF fusion of posed depth views (csrc/fusion_kernels.hip)
     lib.rf_fuse_depth_views.argtypes = [fp, fp, i32p, i32, C.POINTER(RFCamera), vp, vp, vp, f32, f32, f32, u32, vp, vp, vp, vp]
+    # closest points on a mesh (csrc/mesh_distance_kernels.hip)
+    lib.rf_mesh_grid_pairs.argtypes = [vp, i64, vp, i64, fp, f32, i32p, vp, i64, vp, vp, vp, vp]
+    lib.rf_mesh_closest_points.argtypes = [vp, i64, vp, i64, fp, f32, i32p, vp, vp, i64, vp, vp, i64, f32, u32, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
             getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int

@@ -1379,6 +1379,67 @@ def mesh_cluster_keys_raw(vertices: Tensor, origin, r: float, cells, keys: Tenso
     _lib.check(rc, "rf_mesh_cluster_keys")
 
 
+def mesh_grid_pairs_raw(vertices: Tensor, faces: Tensor, origin, h: float, cells, offsets: Tensor, keys: Tensor, pair_faces: Tensor, status: Tensor) -> None:
+    """Enqueue rf_mesh_grid_pairs (include/relu_field.h): the (cell key, face) pairs of every face's box of cells into ``keys`` (int64
+    [P]) and ``pair_faces`` (int32 [P]) from ``offsets[f]`` on (``offsets`` int64 [T + 1]: the exclusive prefix sum of the cells per face,
+    P its last entry).  ``origin`` and ``cells`` are host triples, ``h`` the cell edge.  ``status`` (int32 [1], zeroed by the caller)
+    becomes 1 for a face outside the vertices or not finite, 2 for a face whose count disagrees with ``offsets``.  One launch, no
+    atomics, no host synchronisation.  No autograd."""
+    lib = _lib.load()
+    _check_mesh_array(vertices, torch.float32, 3, "vertices")
+    _check_mesh_array(faces, torch.int64, 3, "faces")
+    _check_mesh_array(offsets, torch.int64, None, "offsets")
+    _check_mesh_array(keys, torch.int64, None, "keys")
+    _check_mesh_array(pair_faces, torch.int32, None, "pair_faces")
+    _check_mesh_array(status, torch.int32, None, "status")
+    if offsets.numel() != faces.shape[0] + 1 or pair_faces.numel() != keys.numel() or status.numel() < 1:
+        raise ValueError("offsets must hold one int64 per face and one more, keys and pair_faces one entry per pair, status one int32")
+    with _span("mesh_grid_pairs", vertices.device):
+        rc = lib.rf_mesh_grid_pairs(vertices.data_ptr(), vertices.shape[0], faces.data_ptr(), faces.shape[0], _lib.float3(origin), float(h),
+                                    (C.c_int32 * 3)(*[int(v) for v in cells]), offsets.data_ptr(), keys.numel(), keys.data_ptr(), pair_faces.data_ptr(),
+                                    status.data_ptr(), _stream(vertices.device))
+    _lib.check(rc, "rf_mesh_grid_pairs")
+
+
+def mesh_closest_points_raw(vertices: Tensor, faces: Tensor, origin, h: float, cells, cell_begin: Tensor, cell_faces: Tensor, points: Tensor,
+                            order: Optional[Tensor], max_distance: float, distance: Tensor, face: Tensor, point: Tensor, rings: Optional[Tensor],
+                            status: Tensor) -> None:
+    """Enqueue rf_mesh_closest_points (include/relu_field.h): per row of ``points`` (float32 [N, 3]) the float32 distance to the mesh
+    into ``distance`` (float32 [N]), the closest face into ``face`` (int64 [N]) and its closest point into ``point`` (float32 [N, 3]);
+    (+inf, -1, NaN) beyond ``max_distance`` (``math.inf``: no limit).  ``cell_begin`` (int32 [cells + 1]) and ``cell_faces`` (int32 [P])
+    are the sorted lists of ``rf_mesh_grid_pairs``; ``order`` (int64 [N] or None) the order in which lanes take the queries; ``rings``
+    (int32 [N] or None) receives the radius at which each query stopped.  ``status`` (int32 [1], zeroed by the caller) becomes non-zero
+    for a non-finite query, a face outside the vertices or a broken list.  One launch, no atomics, no host synchronisation.  No
+    autograd."""
+    lib = _lib.load()
+    _check_mesh_array(vertices, torch.float32, 3, "vertices")
+    _check_mesh_array(faces, torch.int64, 3, "faces")
+    _check_mesh_array(cell_begin, torch.int32, None, "cell_begin")
+    _check_mesh_array(cell_faces, torch.int32, None, "cell_faces")
+    _check_mesh_array(points, torch.float32, 3, "points")
+    _check_mesh_array(distance, torch.float32, None, "distance")
+    _check_mesh_array(face, torch.int64, None, "face")
+    _check_mesh_array(point, torch.float32, 3, "point")
+    _check_mesh_array(status, torch.int32, None, "status")
+    n = points.shape[0]
+    cells = [int(v) for v in cells]
+    if cell_begin.numel() != cells[0] * cells[1] * cells[2] + 1:
+        raise ValueError(f"cell_begin must hold {cells[0] * cells[1] * cells[2] + 1} entries, got {cell_begin.numel()}")
+    if distance.numel() != n or face.numel() != n or point.shape[0] != n or status.numel() < 1:
+        raise ValueError("distance, face and point must hold one row per query and status one int32")
+    for t, dtype, name in ((order, torch.int64, "order"), (rings, torch.int32, "rings")):
+        if t is not None:
+            _check_mesh_array(t, dtype, None, name)
+            if t.numel() != n:
+                raise ValueError(f"{name} must hold {n} entries, got {t.numel()}")
+    with _span("mesh_closest_points", vertices.device):
+        rc = lib.rf_mesh_closest_points(vertices.data_ptr(), vertices.shape[0], faces.data_ptr(), faces.shape[0], _lib.float3(origin), float(h),
+                                        (C.c_int32 * 3)(*cells), cell_begin.data_ptr(), _ptr(cell_faces) if cell_faces.numel() else None, cell_faces.numel(),
+                                        points.data_ptr(), _ptr(order), n, float(max_distance), 0, distance.data_ptr(), face.data_ptr(), point.data_ptr(),
+                                        _ptr(rings), status.data_ptr(), _stream(vertices.device))
+    _lib.check(rc, "rf_mesh_closest_points")
+
+
 def mesh_cluster_vertices_raw(vertices: Tensor, colours: Optional[Tensor], normals: Optional[Tensor], faces: Tensor, members: Tensor,
                               member_begin: Tensor, corners: Tensor, corner_begin: Tensor, cluster_keys: Tensor, origin, h: float, cells,
                               placement: str, regularisation: float, vertices_out: Tensor, colours_out: Optional[Tensor],
