@@ -939,6 +939,38 @@ int rf_mesh_closest_points(const float* vertices_dev, int64_t num_vertices, cons
                            const int64_t* order_dev, int64_t num_points, float max_distance, uint32_t flags, float* distance_dev, int64_t* face_dev,
                            float* point_dev, int32_t* rings_dev, int32_t* status_dev, void* stream);
 
+/* ---- Gradients of the distance to a triangle mesh (csrc/mesh_distance_grad_kernels.hip; DESIGN.md section 28;
+ * docs/mesh_distance_grad_errors.md; thr3ed_atom_amd/mesh_distance_grad.py wires it into autograd, the Chamfer loss and the fit) ------
+ * For query p = points_dev[i] whose closest face, as rf_mesh_closest_points found it, is face_dev[i] = f = (a, b, c): let q be the
+ * closest point of the rule of docs/mesh_distance_errors.md (closest_on_face of csrc/mesh_distance.h), beta its barycentrics in f,
+ * r = p - q per component in float32, len = sqrt(dot(r, r)) with the rule's dot, u = r / len when len > 0 and u = 0 otherwise (the
+ * subgradient at the surface).  With upstream G = grad_distance_dev[i] = dL/d(distance):
+ *   dL/dp = G u,   dL/d(corner k) = -beta_k G u.
+ * Exact wherever the distance is differentiable, in the interior, edge and vertex regions alike: the squared distance is a minimum
+ * over beta, so only the explicit dependence on the corners survives (docs/mesh_distance_grad_errors.md has the argument).
+ * beta comes from the candidate that won, found by running the four candidates in the forward rule's order with its strict <:
+ *   a segment (x, y) with parameter t won:  beta_x = 1 - t, beta_y = t, the third 0;
+ *   the plane candidate won:  with the three edge values of the accept test, E_ab, E_bc, E_ca = dot((y - x) x (q - x), n) at the
+ *     UNCLAMPED q:  S = (E_ab + E_bc) + E_ca, beta_c = E_ab / S, beta_a = E_bc / S, beta_b = E_ca / S;
+ *   S not > 0: the best segment candidate is used instead.
+ * A zero-length edge, a zero-area face or a repeated vertex gives a segment's or a point's beta and never a NaN.  The selected q and
+ * d2 are the forward's bits.
+ * One lane per query, one launch, no atomics, no LDS.  A query with face_dev[i] >= 0 writes grad_points_dev[i] (3 floats),
+ * records_dev[i] (9 floats, corner-major: -beta_k G u), barycentrics_dev[i] (3 floats) and region_dev[i] (0, 1, 2 for the segments
+ * ab, bc, ca; 3 for the plane).  A query with face -1 (nothing within max_distance) writes zeros to grad_points_dev[i] and
+ * barycentrics_dev[i], -1 to region_dev[i] and does NOT write its record.  A face id >= num_faces or a vertex index outside
+ * [0, num_vertices) sets status_dev[0] (int32, zeroed by the caller) to 1 and writes zeros (region -1).  Each of the four outputs may
+ * be NULL.  The per-vertex sum of the records is rf_mesh_geometry_backward_gather's, with num_pixels = num_points and hit_pixels =
+ * the queries that have a face, stably sorted by face.
+ * Before any launch, in this order: RF_ERR_NULL_POINTER (status_dev; vertices_dev / faces_dev with num_faces > 0; points_dev,
+ * face_dev, grad_distance_dev with num_points > 0; all four outputs NULL with num_points > 0), RF_ERR_BAD_SHAPE (a negative count;
+ * num_vertices, num_faces or num_points >= 2^31), RF_ERR_UNSUPPORTED (any flag bit: none is defined); then num_points == 0 or
+ * num_faces == 0 return RF_OK without a launch.  (Added to ABI version 4 compatibly: no existing struct or signature changed.) */
+int rf_mesh_closest_gradients(const float* vertices_dev, int64_t num_vertices, const int64_t* faces_dev, int64_t num_faces,
+                              const float* points_dev, const int64_t* face_dev, const float* grad_distance_dev, int64_t num_points,
+                              uint32_t flags, float* grad_points_dev, float* records_dev, float* barycentrics_dev,
+                              int32_t* region_dev, int32_t* status_dev, void* stream);
+
 /* The loss of the training iteration (modules/trainers.py:311-317, 329-336) in one launch:
  * grad_colour_dev [N,3] = scale * d(mean |colour - target|)/d colour = scale * sign(colour - target) / (3N);
  * sums_dev[0] += sum |colour - target|, sums_dev[1] += sum (colour - target)^2  (L1 loss and MSE/PSNR for

@@ -9,7 +9,9 @@ accumulated weight over a turn-table of views, through the anti-aliased coverage
 The views are those of scripts/render_mesh.py and scripts/bake_texture.py (--views N frames at --camera_pitch; the checkpoint's camera
 unless --view_height / --view_width / --view_focal say otherwise).  --max_move_voxels limits how far a vertex may go from where it
 started, in (smallest) voxel edges; --distance_to_input prints how far the fitted surface lies from the input one (its Hausdorff distance
-is the guard against a too large limit).  Bake textures AFTER the fit (scripts/bake_texture.py), so that they see the fitted surface.
+is the guard against a too large limit).  --target_mesh raw.ply --chamfer_weight W adds W x the Chamfer distance to that surface, in
+mean edge lengths, to the loss (rf.MeshChamferLoss with --chamfer_samples samples per side): the surface the mesh
+was simplified from, which the views see only in part.  Bake textures AFTER the fit (scripts/bake_texture.py), so that they see the fitted surface.
 """
 import os
 import sys
@@ -42,6 +44,9 @@ from thr3ed_atom_amd.mesh_distance import format_mesh_distance  # noqa: E402
 @click.option("--view_width", type=click.IntRange(min=1), default=None, required=False, help="image width of the views (default: the checkpoint's camera)")
 @click.option("--view_focal", type=click.FLOAT, default=None, required=False, help="focal length of the views in pixels (default: the checkpoint's camera)")
 @click.option("--cull_backfaces", is_flag=True, default=False, help="draw only the faces whose outside looks at the camera")
+@click.option("--target_mesh", type=click.Path(file_okay=True, dir_okay=False), default=None, required=False, help="a .ply surface the vertices are also pulled towards (with --chamfer_weight)")
+@click.option("--chamfer_weight", type=click.FloatRange(min=0.0), default=0.0, required=False, help="weight of the Chamfer distance to --target_mesh, measured in mean edge lengths")
+@click.option("--chamfer_samples", type=click.IntRange(min=1), default=100_000, required=False, help="surface samples per side of the Chamfer term")
 @click.option("--distance_to_input", is_flag=True, default=False, help="print the surface distance of the output against the input (Chamfer, Hausdorff lower bound; rf.mesh_distance)")
 # fmt: on
 def main(**kwargs) -> None:
@@ -58,10 +63,15 @@ def main(**kwargs) -> None:
     radius = (extra or {}).get("hemispherical_radius", 4.0311)
     poses = rf.get_thre360_animation_poses(radius, config["camera_pitch"], config["views"] + 1)  # (the path drops its last frame)
     limit = config["max_move_voxels"] * min(grid.voxel_size)
+    target = None
+    if config["target_mesh"] is not None:
+        target_vertices, _, _, target_faces = read_ply(config["target_mesh"])
+        target = rf.Mesh(on_device(target_vertices), on_device(target_faces), None, None)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     fit = rf.fit_mesh_to_field_views(mesh, model, poses, intr, iterations=config["iterations"], lr=config["lr"], depth_weight=config["depth_weight"],
-                                     mask_weight=config["mask_weight"], laplacian_weight=config["laplacian_weight"], max_move=limit, cull_backfaces=config["cull_backfaces"])
+                                     mask_weight=config["mask_weight"], laplacian_weight=config["laplacian_weight"], max_move=limit, cull_backfaces=config["cull_backfaces"],
+                                     target_mesh=target, chamfer_weight=config["chamfer_weight"], chamfer_samples=config["chamfer_samples"])
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(os.path.dirname(os.path.abspath(config["output_path"])), exist_ok=True)

@@ -7,7 +7,9 @@ by vertex clustering with quadric-error representatives (thr3ed_atom_amd.mesh_si
 
 The PLY's uint8 colours are read as colour / 255 and its normals as they are: all-zero normals and all-255 colours -- what write_ply
 stores for a mesh without them -- pass through as data.  --distance_to_input prints how far the result lies from the input (DESIGN.md
-section 27).  Opposed face pairs of collapsed thin sheets are kept; this is vertex
+section 27).  --fit_to_input N pulls the result back onto the input surface with N Adam steps on its vertices against the Chamfer
+distance to the input (rf.fit_mesh_to_mesh) before it is written; with --distance_to_input the distance is printed
+before and after.  Opposed face pairs of collapsed thin sheets are kept; this is vertex
 clustering, not edge collapse.
 """
 import os
@@ -32,6 +34,7 @@ from thr3ed_atom_amd.mesh_distance import format_mesh_distance  # noqa: E402
 @click.option("--target_faces", type=click.IntRange(min=0), default=None, required=False, help="the finest cells that leave at most this many faces")
 @click.option("--placement", type=click.Choice(["quadric", "mean"]), default="quadric", required=False, help="where a cluster's vertex goes")
 @click.option("--regularisation", type=click.FloatRange(min=1e-6, max=1.0), default=1e-3, required=False, help="pull of the quadric minimiser towards the cluster's mean vertex")
+@click.option("--fit_to_input", type=click.IntRange(min=0), default=0, required=False, help="Adam steps that pull the output's vertices back onto the input surface (rf.fit_mesh_to_mesh; 0: off)")
 @click.option("--distance_to_input", is_flag=True, default=False, help="print the surface distance of the output against the input (Chamfer, Hausdorff lower bound; rf.mesh_distance)")
 # fmt: on
 def main(**kwargs) -> None:
@@ -48,11 +51,20 @@ def main(**kwargs) -> None:
                                   regularisation=config["regularisation"], return_stats=True)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    fit = None
+    if config["fit_to_input"]:
+        if config["distance_to_input"]:
+            print("before the fit: " + format_mesh_distance(rf.mesh_distance(out, mesh), "output", "input"))
+        fit = rf.fit_mesh_to_mesh(out, mesh, iterations=config["fit_to_input"])
+        out = fit.mesh
     os.makedirs(os.path.dirname(os.path.abspath(config["output_path"])), exist_ok=True)
     rf.write_ply(out, config["output_path"])
     print(f"{config['placement']}, cell size {stats.cell_size:.6g}: V = {len(mesh.vertices)} -> {len(out.vertices)}, T = {len(mesh.faces)} -> {len(out.faces)} "
           f"({stats.collapsed_faces} collapsed, {stats.merged_duplicates} duplicates merged, {stats.clusters} occupied cells) "
           f"in {1e3 * dt:.1f} ms (incl. host synchronisation) -> {config['output_path']}")
+    if fit is not None and len(fit.history):
+        print(f"fit to the input: loss {float(fit.history[0]):.6g} -> {float(fit.history[-1]):.6g} in {len(fit.history)} iterations; vertices moved "
+              f"{float(fit.moved.mean()):.4g} on average, at most {float(fit.moved.max()):.4g}")
     if config["distance_to_input"]:
         print(format_mesh_distance(rf.mesh_distance(out, mesh), "output", "input"))
 

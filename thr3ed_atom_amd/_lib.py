@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip", "mesh_distance_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip", "mesh_distance_kernels.hip", "mesh_distance_grad_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -124,6 +124,7 @@ EXPORTED_SYMBOLS = [
     "rf_fuse_depth_views",
     "rf_mesh_grid_pairs",
     "rf_mesh_closest_points",
+    "rf_mesh_closest_gradients",
 ]
 
 
@@ -421,6 +422,8 @@ def load() -> C.CDLL:
     # closest points on a mesh (csrc/mesh_distance_kernels.hip)
     lib.rf_mesh_grid_pairs.argtypes = [vp, i64, vp, i64, fp, f32, i32p, vp, i64, vp, vp, vp, vp]
     lib.rf_mesh_closest_points.argtypes = [vp, i64, vp, i64, fp, f32, i32p, vp, vp, i64, vp, vp, i64, f32, u32, vp, vp, vp, vp, vp, vp]
+    # gradients of the distance to a mesh (csrc/mesh_distance_grad_kernels.hip)
+    lib.rf_mesh_closest_gradients.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, u32, vp, vp, vp, vp, vp, vp]
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
             getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int

@@ -7,8 +7,10 @@ face goes through one float32 rule, so the result does not depend on the lattice
 brute force, included -- gives the same bits.  docs/mesh_distance_errors.md has the rule, the error bound and the proof of the stop
 test, tests/mesh_distance_model.py the numpy model, DESIGN.md section 27 the measurements.
 
-Not done here: gradients of the distance (a Chamfer loss for ``fit_mesh_to_views``), signed distance and inside / outside, a BVH for
-meshes whose face sizes vary by orders of magnitude (one lattice serves all faces), point-cloud-to-point-cloud distance."""
+Gradients of the distance, the Chamfer loss and the fit built on them live in thr3ed_atom_amd/mesh_distance_grad.py.
+
+Not done here: signed distance and inside / outside, a BVH for meshes whose face sizes vary by orders of magnitude (one lattice
+serves all faces), point-cloud-to-point-cloud distance."""
 import math
 from typing import NamedTuple, Optional, Sequence, Tuple
 

@@ -35,6 +35,29 @@ class MeshFit(NamedTuple):
     moved: Tensor    # [V] float32: how far each vertex went from its start
 
 
+def corner_slot_lists(faces: Tensor, V: int) -> Tuple[Tensor, Tensor]:
+    """(corner slots int32 [3 T], vertex offsets int64 [V + 1]) of int64 ``faces`` [T, 3]: the slots 3 face + corner sorted by the vertex
+    they name (stable) -- the second list of rf_mesh_geometry_backward_gather"""
+    flat = faces.view(-1)
+    _, order = torch.sort(flat, stable=True)
+    return order.to(torch.int32).contiguous(), _marshal.segment_offsets(flat.clamp(0, max(V - 1, 0)), V)
+
+
+def gather_vertex_gradients(records: Tensor, entries: Tensor, face_offsets: Tensor, num_faces: int, slots: Tensor, vertex_offsets: Tensor, V: int,
+                            long_segment: int, status: Tensor) -> Tensor:
+    """[V, 3] float32 from 9-float ``records`` [P, 9]: rf_mesh_geometry_backward_gather, the two segmented sums without atomics
+    (``entries`` int32: the rows that count, sorted by face, stably; ``face_offsets`` int64 [T + 1]).  What the mesh render's and the
+    mesh distance's backward share."""
+    dev = records.device
+    face_grads = torch.empty((num_faces, 9), dtype=torch.float32, device=dev)
+    grad = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    rc = _lib.load().rf_mesh_geometry_backward_gather(records.data_ptr(), int(records.shape[0]), entries.data_ptr(), int(entries.shape[0]), face_offsets.data_ptr(), num_faces,
+                                                      slots.data_ptr(), vertex_offsets.data_ptr(), V, long_segment, 0, face_grads.data_ptr(), grad.data_ptr(),
+                                                      status.data_ptr(), _marshal.stream(dev))
+    _lib.check(rc, "rf_mesh_geometry_backward_gather")
+    return grad
+
+
 class _Render(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices: Tensor, renderer: "MeshGeometryRenderer"):
@@ -111,9 +134,7 @@ class MeshGeometryRenderer:
     def corner_lists(self, V: int):
         """(corner slots int32 [3 T], vertex offsets int64 [V + 1]): the slots 3 face + corner sorted by the vertex they name (stable)"""
         if self._corners is None or self._corners[2] != V:
-            flat = self.faces.view(-1)
-            _, order = torch.sort(flat, stable=True)
-            self._corners = (order.to(torch.int32).contiguous(), _marshal.segment_offsets(flat.clamp(0, max(V - 1, 0)), V), V)
+            self._corners = (*corner_slot_lists(self.faces, V), V)
         return self._corners[0], self._corners[1]
 
     def hit_lists(self, face_ids: Tensor):
@@ -136,13 +157,7 @@ class MeshGeometryRenderer:
     def _gather(self, records: Tensor, hit_pixels: Tensor, face_offsets: Tensor, V: int) -> Tensor:
         """stage 2: [V, 3] float32"""
         slots, vertex_offsets = self.corner_lists(V)
-        face_grads = torch.empty((self.T, 9), dtype=torch.float32, device=self.device)
-        grad = torch.empty((V, 3), dtype=torch.float32, device=self.device)
-        rc = _lib.load().rf_mesh_geometry_backward_gather(records.data_ptr(), self.P, hit_pixels.data_ptr(), int(hit_pixels.shape[0]), face_offsets.data_ptr(), self.T,
-                                                          slots.data_ptr(), vertex_offsets.data_ptr(), V, self.long_segment, 0, face_grads.data_ptr(), grad.data_ptr(),
-                                                          self.status.data_ptr(), _marshal.stream(self.device))
-        _lib.check(rc, "rf_mesh_geometry_backward_gather")
-        return grad
+        return gather_vertex_gradients(records, hit_pixels, face_offsets, self.T, slots, vertex_offsets, V, self.long_segment, self.status)
 
     def _backward(self, vertices: Tensor, face_ids: Tensor, coverage: Tensor, grad_depth: Tensor, grad_coverage: Tensor) -> Tensor:
         V = int(vertices.shape[0])
@@ -234,13 +249,16 @@ def fit_loss(depth: Tensor, coverage: Tensor, face_ids: Tensor, depths: Tensor, 
 
 def fit_mesh_to_views(mesh: Mesh, depths, alphas, poses: Sequence, camera_intrinsics, *, iterations: int = 200, lr: Optional[float] = None, depth_weight: float = 1.0,
                       mask_weight: float = 1.0, laplacian_weight: float = DEFAULT_LAPLACIAN_WEIGHT, max_move: Optional[float] = None, near: float = 0.0,
-                      cull_backfaces: bool = False, callback: Optional[Callable[[int, Tensor], None]] = None) -> MeshFit:
+                      cull_backfaces: bool = False, callback: Optional[Callable[[int, Tensor], None]] = None, target_mesh: Optional[Mesh] = None,
+                      chamfer_weight: float = 0.0, chamfer_samples: int = 100_000) -> MeshFit:
     """Move ``mesh.vertices`` so that ``MeshGeometryRenderer``'s images match posed targets.  ``depths`` [N, H, W] (or N [H, W]): the
     ray-parameter depth per pixel, as ``RenderOut.depth`` holds it; ``alphas`` [N, H, W]: the coverage in [0, 1]; ``poses`` N CameraPose
     of one ``camera_intrinsics``.  The loss is ``mask_weight`` mean((A - alpha)^2) over all pixels + ``depth_weight`` mean |D - depth|
     over the pixels that are hit and have alpha > 1/2 + ``laplacian_weight`` mean_i |L(v)_i - L(v_start)_i|^2 / (mean edge length)^2
     with L(v)_i = v_i - the mean of its edge neighbours: the Laplacian is held to the INITIAL mesh's, so a mesh that already fits is
-    a fixed point, and it is measured in edge lengths, so the weight means the same at every scale.
+    a fixed point, and it is measured in edge lengths, so the weight means the same at every scale.  With ``target_mesh`` and a
+    positive ``chamfer_weight`` the loss gains ``chamfer_weight`` x ``MeshChamferLoss(faces, target_mesh, samples=chamfer_samples)(v)`` /
+    (mean edge length), the data term of ``fit_mesh_to_mesh``; with ``target_mesh=None`` or weight 0 nothing is built or launched for it.
 
     ``torch.optim.Adam`` on the vertices; ``lr`` defaults to 0.05 x the mean edge length.  ``max_move`` (world units): after each step
     every vertex is pulled back into the ball of that radius round its start.  ``iterations=0`` returns the mesh itself.
@@ -258,6 +276,7 @@ def fit_mesh_to_views(mesh: Mesh, depths, alphas, poses: Sequence, camera_intrin
     lr = None if lr is None else _marshal.positive(lr, "lr")
     max_move = None if max_move is None else _marshal.positive(max_move, "max_move")
     depth_weight, mask_weight, laplacian_weight = _weight(depth_weight, "depth_weight"), _weight(mask_weight, "mask_weight"), _weight(laplacian_weight, "laplacian_weight")
+    chamfer_weight = _weight(chamfer_weight, "chamfer_weight")
     H, W = int(camera_intrinsics[0]), int(camera_intrinsics[1])
     dev, V = vertices.device, int(vertices.shape[0])
     renderer = MeshGeometryRenderer(faces, poses, camera_intrinsics, near=near, cull_backfaces=cull_backfaces)
@@ -285,11 +304,17 @@ def fit_mesh_to_views(mesh: Mesh, depths, alphas, poses: Sequence, camera_intrin
     start_laplacian = laplacian(start)
     param = start.clone().requires_grad_(True)
     optimiser = torch.optim.Adam([param], lr=lr)
+    chamfer = None
+    if target_mesh is not None and chamfer_weight > 0.0:
+        from .mesh_distance_grad import MeshChamferLoss  # (it imports this module)
+        chamfer = MeshChamferLoss(faces, target_mesh, samples=chamfer_samples)
     losses = []
     for it in range(iterations):
         optimiser.zero_grad(set_to_none=True)
         depth, coverage = renderer(param)
         value = fit_loss(depth, coverage, renderer.last_face_ids, depths, alphas, depth_weight, mask_weight)
+        if chamfer is not None:
+            value = value + chamfer_weight * chamfer(param) / edge_length
         if laplacian_weight > 0.0:
             value = value + laplacian_weight * ((laplacian(param) - start_laplacian) ** 2).sum(1).mean() / (edge_length * edge_length)
         value.backward()
