@@ -25,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import thr3ed_atom_amd as rf  # noqa: E402
 from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
 from thr3ed_atom_amd.mesh_distance import format_mesh_distance  # noqa: E402
+from thr3ed_atom_amd.mesh_sign import format_signed_mean, signed_mean_against  # noqa: E402
 
 
 # fmt: off
@@ -83,6 +84,9 @@ def main(**kwargs) -> None:
           f"{float(fit.moved.max()) if len(mesh.vertices) else 0.0:.4g} (limit {limit:.4g}) in {dt:.2f} s (incl. the field's renders) -> {config['output_path']}")
     if config["distance_to_input"]:
         print(format_mesh_distance(rf.mesh_distance(fit.mesh, mesh), "output", "input"))
+        signed = signed_mean_against(fit.mesh, mesh)  # (None unless the input is a closed oriented surface)
+        if signed is not None:
+            print(format_signed_mean(signed))
 
 
 if __name__ == "__main__":

@@ -24,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import thr3ed_atom_amd as rf  # noqa: E402
 from thr3ed_atom_amd.mesh import read_ply  # noqa: E402
 from thr3ed_atom_amd.mesh_distance import format_mesh_distance  # noqa: E402
+from thr3ed_atom_amd.mesh_sign import format_signed_mean, signed_mean_against  # noqa: E402
 
 
 # fmt: off
@@ -67,6 +68,9 @@ def main(**kwargs) -> None:
               f"{float(fit.moved.mean()):.4g} on average, at most {float(fit.moved.max()):.4g}")
     if config["distance_to_input"]:
         print(format_mesh_distance(rf.mesh_distance(out, mesh), "output", "input"))
+        signed = signed_mean_against(out, mesh)  # (None unless the input is a closed oriented surface)
+        if signed is not None:
+            print(format_signed_mean(signed))
 
 
 if __name__ == "__main__":

@@ -54,6 +54,8 @@ from .mesh_fit import MeshFit, MeshGeometryRenderer, fit_mesh_to_field_views, fi
 from .fusion import FusedVolume, fuse_depth_views, fuse_field_views  # noqa: F401
 from .mesh_distance import ClosestPoints, DirectedDistance, MeshDistance, MeshDistanceGrid, ThresholdScore, closest_points_on_mesh, mesh_distance, sample_mesh_surface  # noqa: F401
 from .mesh_distance_grad import MeshChamferLoss, fit_mesh_to_mesh, mesh_surface_points, point_mesh_distance  # noqa: F401
+from .mesh_sign import (MeshSDF, MeshSignGrid, MeshTopology, SignedClosestPoints, SignedDirected, SignedMeshDistance, mesh_contains, mesh_signed_distance,  # noqa: F401
+                        mesh_to_sdf, mesh_topology, point_mesh_signed_distance, signed_mesh_distance)
 from .ops import distortion_loss, render_geometry, total_variation  # noqa: F401
 from .metrics import ssim  # noqa: F401
 from .trainers import evaluate_sh_vox_grid_vol_mod_with_posed_images  # noqa: F401

@@ -12,7 +12,7 @@ CSRC_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 LIB_NAME = "librelu_field_hip.so"
 LIB_PATH = os.environ.get("RF_LIB_PATH") or os.path.join(CSRC_DIR, LIB_NAME)  # RF_LIB_PATH: development builds (tools/)
-SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip", "mesh_distance_kernels.hip", "mesh_distance_grad_kernels.hip"]
+SOURCES = ["relu_field_kernels.hip", "grid_kernels.hip", "ray_walk_kernels.hip", "ray_grad_kernels.hip", "mesh_kernels.hip", "image_kernels.hip", "vq_kernels.hip", "component_kernels.hip", "mesh_simplify_kernels.hip", "texture_kernels.hip", "mesh_raster_kernels.hip", "texture_views_kernels.hip", "texture_fit_kernels.hip", "mesh_fit_kernels.hip", "fusion_kernels.hip", "mesh_distance_kernels.hip", "mesh_distance_grad_kernels.hip", "mesh_sign_kernels.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
 ABI_VERSION = 4  # RF_ABI_VERSION of include/relu_field.h (4: compact records + compacted sample cache, x-slab-major keys, brick ranges)
@@ -125,6 +125,15 @@ EXPORTED_SYMBOLS = [
     "rf_mesh_grid_pairs",
     "rf_mesh_closest_points",
     "rf_mesh_closest_gradients",
+]
+
+EXT_ABI_VERSION = 1  # RF_EXT_ABI_VERSION of include/relu_field_ext.h
+# The list above is closed (include/relu_field.h is frozen with it): entry points added from here on are declared in
+# include/relu_field_ext.h and listed here.
+EXTENSION_SYMBOLS = [
+    "rf_ext_abi_version",
+    "rf_mesh_face_pseudonormals",
+    "rf_mesh_signed_distance",
 ]
 
 
@@ -290,9 +299,9 @@ ABI_STRUCTS = [RFGrid, RFRayBatch, RFRenderOut, RFRenderGrads, RFBrickList, RFAd
 
 
 def build_inputs():
-    """Every file whose modification makes the library stale: the units of SOURCES, every private header of csrc/, the public header."""
+    """Every file whose modification makes the library stale: the units of SOURCES, every private header of csrc/, the two public headers."""
     headers = sorted(f for f in os.listdir(CSRC_DIR) if f.endswith(".h"))
-    return [os.path.join(CSRC_DIR, f) for f in SOURCES + headers] + [os.path.join(INCLUDE_DIR, "relu_field.h")]
+    return [os.path.join(CSRC_DIR, f) for f in SOURCES + headers] + [os.path.join(INCLUDE_DIR, "relu_field.h"), os.path.join(INCLUDE_DIR, "relu_field_ext.h")]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -424,6 +433,14 @@ def load() -> C.CDLL:
     lib.rf_mesh_closest_points.argtypes = [vp, i64, vp, i64, fp, f32, i32p, vp, vp, i64, vp, vp, i64, f32, u32, vp, vp, vp, vp, vp, vp]
     # gradients of the distance to a mesh (csrc/mesh_distance_grad_kernels.hip)
     lib.rf_mesh_closest_gradients.argtypes = [vp, i64, vp, i64, vp, vp, vp, i64, u32, vp, vp, vp, vp, vp, vp]
+    # the sign of the distance to a closed mesh (csrc/mesh_sign_kernels.hip; include/relu_field_ext.h)
+    lib.rf_ext_abi_version.argtypes = []
+    lib.rf_mesh_face_pseudonormals.argtypes = [vp, i64, vp, i64, u32, vp, vp, vp, vp]
+    lib.rf_mesh_signed_distance.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, i64, u32, vp, vp, vp, vp, vp]
+    for name in EXTENSION_SYMBOLS:
+        getattr(lib, name).restype = C.c_int
+    if lib.rf_ext_abi_version() != EXT_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH}: extension ABI version {lib.rf_ext_abi_version()} != {EXT_ABI_VERSION} (stale build? run __graft_entry__.build())")
     for name in EXPORTED_SYMBOLS:
         if name not in ("rf_error_string",):
             getattr(lib, name).restype = C.c_int64 if name in ("rf_brick_split_scratch_bytes", "rf_mesh_tiles", "rf_ssim_tiles") else C.c_int

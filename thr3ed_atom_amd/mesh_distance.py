@@ -7,9 +7,10 @@ face goes through one float32 rule, so the result does not depend on the lattice
 brute force, included -- gives the same bits.  docs/mesh_distance_errors.md has the rule, the error bound and the proof of the stop
 test, tests/mesh_distance_model.py the numpy model, DESIGN.md section 27 the measurements.
 
-Gradients of the distance, the Chamfer loss and the fit built on them live in thr3ed_atom_amd/mesh_distance_grad.py.
+Gradients of the distance, the Chamfer loss and the fit built on them live in thr3ed_atom_amd/mesh_distance_grad.py, the signed
+distance and inside / outside in thr3ed_atom_amd/mesh_sign.py.
 
-Not done here: signed distance and inside / outside, a BVH for meshes whose face sizes vary by orders of magnitude (one lattice
+Not done here: a BVH for meshes whose face sizes vary by orders of magnitude (one lattice
 serves all faces), point-cloud-to-point-cloud distance."""
 import math
 from typing import NamedTuple, Optional, Sequence, Tuple

@@ -10,7 +10,7 @@ include/relu_field.h has the contract, docs/mesh_distance_grad_errors.md the env
 tests/mesh_distance_grad_model.py the numpy model, DESIGN.md section 28 the measurements.  There is no CPU path.
 
 Not done here: warm-starting a query from the previous iteration's face, fusing the sampler's records into the kernel, point clouds
-as targets, signed distance, a normal-consistency term."""
+as targets, a normal-consistency term.  (Signed distance: thr3ed_atom_amd/mesh_sign.py.)"""
 import math
 from typing import Callable, Optional, Tuple
 
